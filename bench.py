@@ -12,9 +12,13 @@ encode B queries + B*(1+K) passages (Llama-3.2-1B architecture, bf16, random ini
 AdamW (HIP, one launch).  value = N * B * (1 + K) * steps / time.  Weak scaling: per-GPU work is fixed.
 
 Workload at N = 1: BASELINE.json configs[1] (q_len 1280, p_len 4096, K = 5, B = 8, in-batch negatives, T = 0.02).
-The JSON line also carries `roofline` (dominant hand-written kernel of the timed step, HIP-event timed live),
-`kernels` (every hand-written entry point in the step), `roofline_sweep` (the similarity+InfoNCE kernel on the
-scaled shapes of SURVEY.md §8d where it is MFMA-bound) and `cpu_baseline` (the oracle's step on the host cores).
+The JSON line also carries `roofline` (dominant hand-written kernel of the timed step, HIP-event timed live) and
+`kernels` (every hand-written entry point in the step).  With `--full` it also carries `roofline_sweep` (the
+similarity+InfoNCE kernel on the scaled shapes of SURVEY.md §8d where it is MFMA-bound), `cpu_baseline` (the oracle's
+step on the host cores) and `step_loss_parity`; a plain run sets up, warms up, times the steps and prints the line.
+
+`--dump-outputs DIR` writes what the last timed step handed its caller as DIR/<name>.npy (float32; `step_outputs`), for
+comparing two builds output for output: the inputs and initial weights are seeded, identical from run to run.
 """
 from __future__ import annotations
 
@@ -792,8 +796,46 @@ from rankpo_amd.memory import (PLAN_HBM_FRACTION, PRESIZE_TIGHT_FRACTION, DGU_T_
                                admit_transposed_dgu, may_retry_after_oom)
 
 
+DUMP_SAMPLE = 1 << 21          # parameters sampled per dumped buffer (8 MB as float32)
+DUMP_MAX_BYTES = 64 * 2 ** 20
+
+
+def write_outputs(out_dir, arrays):
+    """`--dump-outputs`: every array as out_dir/<name>.npy in float32, 64 MB in all at most."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs, more than {DUMP_MAX_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"[bench] outputs of the last timed step: {', '.join(f'{k}{list(a.shape)}' for k, a in arrays.items())} -> {out_dir}",
+          file=sys.stderr, flush=True)
+
+
+def step_outputs(ts, loss):
+    """What the last timed training step handed its caller: the loss it returned, the gradient norm the clip used, and the
+    parameters it updated -- the bf16 (or f32) parameters and, where the optimizer keeps them, the float32 master weights, which
+    carry updates smaller than a bf16 ulp.  A full parameter set is gigabytes, so both are sampled at the same DUMP_SAMPLE flat
+    indices: numpy.random.default_rng(0).choice(numel, DUMP_SAMPLE, replace=False), sorted -- the same indices in every run of
+    the same workload."""
+    opt = ts.opt
+    flat = opt.flat_param
+    n = flat.numel()
+    idx = np.arange(n) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(0).choice(n, size=DUMP_SAMPLE, replace=False))
+    idx_d = torch.from_numpy(idx).to(flat.device)
+    out = {"loss": loss.detach().float().reshape(1).cpu().numpy(),
+           "params_sample": flat[idx_d].float().cpu().numpy()}
+    if opt.last_grad_norm is not None:
+        out["grad_norm"] = opt.last_grad_norm.detach().float().reshape(1).cpu().numpy()
+    if opt.master is not None and not opt.partition:
+        out["master_params_sample"] = opt.master[idx_d].cpu().numpy()
+    return out
+
+
 def inference_main(args, device, wd, rank, arch):
-    """--workload encode: ModelForInference.encode and the exact top-k search, ONE JSON line (bench_inference.py)."""
+    """--workload encode: ModelForInference.encode and, with --full, the exact top-k search and the oracle leg, ONE JSON line
+    (bench_inference.py).  The pre-tokenised encode reps always run: the line's `roofline` is taken from them."""
     import bench_inference as BI
     from rankpo_amd import _lib
     from rankpo_amd.encoder import build_encoder
@@ -808,10 +850,16 @@ def inference_main(args, device, wd, rank, arch):
     note = lambda m: print(f"[bench r{rank} {time.strftime('%H:%M:%S')}] {m}", file=sys.stderr, flush=True)
     small = arch != "llama-3.2-1b"
     wd.phase("encode()", 1500)
+    outputs = {} if args.dump_outputs else None
     enc_block = BI.encode_block(cfg, enc, device, note, reps=max(1, args.steps // 2), n_query=128 if small else 256,
-                                n_passage=128 if small else 256, oracle=not args.no_cpu_baseline, cores=usable_cores()[0])
-    wd.phase("search", 600)
-    search = BI.search_block(device, timed, note, ntotal=100_000 if small else 1_000_000)
+                                n_passage=128 if small else 256, oracle=args.full and not args.no_cpu_baseline,
+                                cores=usable_cores()[0], outputs=outputs)
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs)
+    search = None
+    if args.full:
+        wd.phase("search", 600)
+        search = BI.search_block(device, timed, note, ntotal=100_000 if small else 1_000_000)
     wd.done()
     pas = enc_block["passages"]
     line = {"metric": "sentences/sec of ModelForInference.encode (passages <= 4096 tokens, batch 64), tokeniser included",
@@ -862,6 +910,11 @@ def main():
                     help="A/B: round 1's dK/dV work list (heaviest blocks first, ascending sweep) instead of group order with a heaviest-first tail")
     ap.add_argument("--dkdv-tail", type=float, default=None,
                     help="A/B: fraction of every XCD's dK/dV work that runs heaviest-first behind the group-ordered part (ops.ATTN_GROUP_TAIL)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the legs that the headline figure does not need: the roofline sweep, the "
+                         "cpu baseline and the step-loss parity checks (encode workload: the search block and the oracle leg)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, < 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sweep", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
@@ -901,7 +954,7 @@ def main():
                     help="write torch.cuda.memory_summary() + the allocator's totals after the allocator pre-size step to this file "
                          "(what the worst-case peak is made of: profiles/r05_cfg5_memory_summary.txt)")
     ap.add_argument("--headline-parity", default="auto", choices=("auto", "on", "off"),
-                    help="N = 1: second step-parity sample at the headline size (2 queries <= q_len + 6 passages <= p_len tokens "
+                    help="N = 1: second step-parity sample at the headline size (4 queries <= q_len + 12 passages <= p_len tokens "
                          "through ALL blocks, float32 oracle on the device pinned to the host); auto = on for the Llama-3.2-1B "
                          "workloads, where it fits beside the training state")
     args = ap.parse_args()
@@ -1215,6 +1268,8 @@ def main():
     timed.enabled = False
     bal_state["on"] = balance
     note(f"timed {args.steps} steps in {elapsed:.3f} s" + (f" (re-deal on: {seg_times[0]:.3f} s, off: {seg_times[1]:.3f} s)" if split_balance else ""))
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, step_outputs(ts, losses[-1]))
     comm = None
     if multi:
         wd.phase("comm block", 300)
@@ -1349,11 +1404,11 @@ def main():
                        "standalone_avg_us": a["avg_us"], "standalone_frac_mfma": a["frac_mfma"], "standalone_calls": a["calls"],
                        "in_step_over_standalone": round(instep[name]["avg_us"] / a["avg_us"], 4)}
                 for name, a in alone.items() if name in instep}
-        if world == 1 and not args.no_sweep:
+        if world == 1 and args.full and not args.no_sweep:
             wd.phase("roofline sweep (similarity + InfoNCE kernel)", 600)
             out["roofline_sweep"] = sweep(timed, device)
             note("sweep done")
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             wd.phase("cpu baseline (oracle on the host cores)", 1200)
             note("cpu baseline (oracle on host cores) ...")
             dt, times, toks, (cores, cores_how), sample_batch, ref, fit = cpu_baseline(
@@ -1409,7 +1464,7 @@ def main():
                                            "failed": out["step_loss_parity"]["failed"] + ["headline:" + f for f in hp["failed"]],
                                            "short_sample": out["step_loss_parity"], "headline_sample": hp,
                                            "samples": "short_sample: the cpu_baseline rows (oracle on the host end to end); "
-                                                      "headline_sample: one full-length query and passage row among 2 + 6 rows "
+                                                      "headline_sample: one full-length query and passage row among 4 + 12 rows (the first 2 + 6: `first_block_*`) "
                                                       "through all blocks (oracle on the device, pinned to the host)"}
             if not out["step_loss_parity"]["pass"]:
                 print(json.dumps(out), flush=True)

@@ -6,7 +6,7 @@
            tokenisation cost is a real one).  Reported: sentences/s and real tokens/s END TO END (tokeniser included, as a user
            gets it), the same from host tensors that are already tokenised (the device-side ceiling), the split of the wall
            clock, and the forward's fraction of the bf16 MFMA peak from its algorithmic FLOP on the real tokens.
-           Beside it: the oracle (oracle/encoder_ref.py, float32, host cores) on a bounded sample, timed, with parity.
+           Beside it (`--full`): the oracle (oracle/encoder_ref.py, float32, host cores) on a bounded sample, timed, with parity.
   search : exact inner-product top-k over a 10^6 x 2048 bf16 corpus, k = 100, queries in batches of 256 as the reference's
            `faiss_search` does (utils.py:58-80): similarity (MFMA kernel) + `rpo_topk_merge`; scored pairs/s, corpus GB/s, the
            kernels' own times, and exactness of the winners' values against a full sort on a sample.
@@ -76,7 +76,8 @@ class _Replay:
         return b
 
 
-def encode_block(cfg, enc, device, note, reps=2, batch_size=64, n_query=256, n_passage=256, oracle=True, cores=None):
+def encode_block(cfg, enc, device, note, reps=2, batch_size=64, n_query=256, n_passage=256, oracle=True, cores=None, outputs=None):
+    """`outputs` (a dict, bench.py --dump-outputs): receives the embeddings of the last timed end-to-end encode() of either side."""
     import rankpo_amd
     tok = load_bench_tokenizer()
     inf = rankpo_amd.ModelForInference(encoder=enc, tokenizer=tok, use_bf16=True, device=device.index or 0)
@@ -128,6 +129,8 @@ def encode_block(cfg, enc, device, note, reps=2, batch_size=64, n_query=256, n_p
              f"{n / dev:.1f} sentences/s, forward {flops / dev / 1e12:.0f} TFLOP/s = {flops / dev / 1e12 / MFMA_BF16_PEAK_TFLOPS:.3f} of peak; "
              f"tokeniser alone {t_tok:.2f} s")
         sides[name]["_texts"], sides[name]["_out"] = texts, out
+        if outputs is not None:
+            outputs[f"{name}_embeddings"] = out
     block = {"model": "Llama-3.2-1B architecture, random init, bf16", "tokenizer": "tests/golden/realdata_tokenizer.json (BPE, 4096 words)",
              "driver": "ModelForInference.encode(sentences, batch_size=64, max_length=1280 | 4096) as scripts/evaluate/run_evaluate.sh",
              "host_threads": os.cpu_count()}

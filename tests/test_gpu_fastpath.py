@@ -361,3 +361,44 @@ def test_gradient_checkpointing_enable_plans_from_the_measured_hbm(monkeypatch):
     # a longer batch: re-planned, never fewer checkpointed blocks than before
     enc._checkpointed_blocks(8 * enc.memory_plan.tokens)
     assert enc.memory_plan.checkpoint_blocks >= k_small and enc.memory_plan.tokens == 8 * M.pad_tokens(tok_pad)
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_its_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W` without `--full`: N timed steps (counted by the optimizer launches the line's
+    `kernels` saw), `ms_per_step` in the line, none of the legs that
+    only `--full` runs (sweep, cpu baseline, step parity); `--dump-outputs DIR` writes the last timed step's loss, gradient norm
+    and sampled parameters as float32 .npy files, and a second run with the same arguments (seeded inputs and weights) writes
+    the same values."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    dumps, lines = [], []
+    for run in range(2):
+        d = str(tmp_path / f"run{run}")
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "tiny", "--steps", "3",
+                            "--warmup", "1", "--dump-outputs", d], capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(out) == 1, r.stdout[-2000:]
+        lines.append(out[0])
+        files = sorted(os.listdir(d))
+        assert files == ["grad_norm.npy", "loss.npy", "master_params_sample.npy", "params_sample.npy"], files
+        arrs = {f[:-4]: np.load(os.path.join(d, f)) for f in files}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 * 2 ** 20
+        dumps.append(arrs)
+    for out in lines:
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["unit"] == "pairs/s"
+        # the steps that really ran in the timed region: one AdamW launch and one gradient-norm launch per optimizer step
+        calls = {k["entry"]: k["calls"] for k in out["kernels"]}
+        assert calls["rpo_adamw_step"] == 3 and calls["rpo_sumsq_partial"] == 3, calls
+        assert not {"roofline_sweep", "cpu_baseline", "step_loss_parity"} & set(out), sorted(out)
+    a, b = dumps
+    assert abs(float(a["loss"][0]) - lines[0]["loss_last"]) <= 1e-4 * max(1.0, abs(lines[0]["loss_last"]))
+    assert a["params_sample"].shape == a["master_params_sample"].shape and a["params_sample"].size > 0
+    assert abs(a["loss"][0] - b["loss"][0]) <= 1e-3 * max(1.0, abs(b["loss"][0]))
+    assert abs(a["grad_norm"][0] - b["grad_norm"][0]) <= 1e-2 * b["grad_norm"][0]
+    assert np.allclose(a["master_params_sample"], b["master_params_sample"], rtol=1e-3, atol=1e-6)

@@ -761,6 +761,37 @@ def test_bench_watchdog_names_the_phase_when_a_rank_stalls():
     assert fired == [3] and [n for n, _ in wd2.history] == ["start", "ends"]
 
 
+def test_bench_dump_outputs_sample_and_format(tmp_path):
+    """`bench.py --dump-outputs`: the last step's loss, gradient norm and parameters (bf16 parameters and float32 master weights
+    at the same seeded flat indices, sorted, the same in every run) written as float32 .npy files; more than 64 MB is refused."""
+    import importlib
+    from types import SimpleNamespace
+    B = importlib.import_module("bench")
+    n = B.DUMP_SAMPLE * 3
+    master = torch.linspace(-1.0, 1.0, n)
+    opt = SimpleNamespace(flat_param=master.to(torch.bfloat16), master=master, partition=False,
+                          last_grad_norm=torch.tensor(0.75))
+    ts = SimpleNamespace(opt=opt)
+    out = B.step_outputs(ts, torch.tensor(2.5))
+    assert sorted(out) == ["grad_norm", "loss", "master_params_sample", "params_sample"]
+    assert out["loss"].tolist() == [2.5] and out["grad_norm"].tolist() == [0.75]
+    assert out["params_sample"].shape == out["master_params_sample"].shape == (B.DUMP_SAMPLE,)
+    idx = np.sort(np.random.default_rng(0).choice(n, size=B.DUMP_SAMPLE, replace=False))
+    assert np.array_equal(out["master_params_sample"], master.numpy()[idx])
+    assert np.array_equal(out["params_sample"], master.to(torch.bfloat16).float().numpy()[idx])
+    assert np.array_equal(B.step_outputs(ts, torch.tensor(2.5))["master_params_sample"], out["master_params_sample"])
+    # partitioned optimizer state: the master weights are a shard, only the full parameters are sampled
+    opt.partition = True
+    assert "master_params_sample" not in B.step_outputs(ts, torch.tensor(2.5))
+    B.write_outputs(str(tmp_path / "d"), out)
+    for k, v in out.items():
+        got = np.load(str(tmp_path / "d" / f"{k}.npy"))
+        assert got.dtype == np.float32 and np.array_equal(got, v)
+    with pytest.raises(SystemExit):
+        B.write_outputs(str(tmp_path / "big"), {"x": np.zeros(B.DUMP_MAX_BYTES // 4 + 1, dtype=np.float64)})
+    assert not os.path.exists(str(tmp_path / "big"))
+
+
 def test_bench_lib_switch_really_switches(tmp_path):
     """`bench.py --lib other.so` is the in-step A/B of kernel builds.  Round 3's version set `_lib.LIB_PATH` after the package import
     had loaded and cached the in-tree build: every call still went to the in-tree library and the "A/B" compared it with itself

@@ -8,8 +8,8 @@ timeout -k 10 600 python3 -m pytest tests/test_gpu_kernels.py tests/test_gpu_f16
 tail -3 $o/pytest_gpu.log
 python3 tools/pool_bench.py > $o/pool_ab.md 2> $o/pool_ab.err || true
 cat $o/pool_ab.md
-timeout -k 10 900 python3 bench.py --workload encode --steps 4 > $o/bench_encode.json 2> $o/bench_encode.err || true
+timeout -k 10 900 python3 bench.py --full --workload encode --steps 4 > $o/bench_encode.json 2> $o/bench_encode.err || true
 tail -c 1500 $o/bench_encode.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof_encode -- python3 bench.py --workload encode --steps 2 --no-cpu-baseline > $o/bench_encode_profiled.json 2> $o/bench_encode_profiled.err || true
+rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof_encode -- python3 bench.py --full --workload encode --steps 2 --no-cpu-baseline > $o/bench_encode_profiled.json 2> $o/bench_encode_profiled.err || true
 ls $o/prof_encode/*/ | head
 echo callA done

@@ -7,6 +7,6 @@ timeout -k 10 600 python3 -m pytest tests/test_gpu_inference.py tests/test_gpu_f
 tail -3 $o/pytest.log
 python3 -c "import __graft_entry__ as g; g.smoke()" > $o/smoke.log 2>&1 || true
 tail -2 $o/smoke.log
-python3 bench.py --workload encode --steps 6 > $o/bench_encode.json 2> $o/bench_encode.err
+python3 bench.py --full --workload encode --steps 6 > $o/bench_encode.json 2> $o/bench_encode.err
 grep "encode \|search:" $o/bench_encode.err | cut -c1-260
 echo callE done

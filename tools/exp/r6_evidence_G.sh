@@ -5,7 +5,7 @@ o=gpurun_out/r6_G
 mkdir -p $o
 timeout -k 10 600 python3 -m pytest tests/test_gpu_fastpath.py tests/test_gpu_inference.py -x -q -m gpu > $o/pytest.log 2>&1 || true
 tail -3 $o/pytest.log
-python3 bench.py > $o/bench_default.json 2> $o/bench_default.err
+python3 bench.py --full > $o/bench_default.json 2> $o/bench_default.err
 python3 bench.py --steps 100 --warmup 5 --no-cpu-baseline --no-sweep > $o/bench_cfg2_100_steps.json 2> $o/bench_cfg2_100_steps.err
 python3 - <<'PY'
 import json

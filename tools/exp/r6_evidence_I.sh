@@ -5,7 +5,7 @@ o=gpurun_out/r6_I
 mkdir -p $o
 timeout -k 10 600 python3 -m pytest tests/test_gpu_kernels.py tests/test_gpu_encoder.py tests/test_realdata.py -x -q -m gpu -k "topk or flat_index or search or retriev or metric" > $o/pytest.log 2>&1 || true
 tail -3 $o/pytest.log
-timeout -k 10 900 python3 bench.py --workload encode --steps 2 --no-cpu-baseline > $o/bench_encode.json 2> $o/bench_encode.err || true
+timeout -k 10 900 python3 bench.py --full --workload encode --steps 2 --no-cpu-baseline > $o/bench_encode.json 2> $o/bench_encode.err || true
 grep "search:" $o/bench_encode.err
 python3 -c "
 import json

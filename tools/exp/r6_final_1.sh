@@ -5,8 +5,8 @@ o=gpurun_out/r6_F1
 mkdir -p $o
 timeout -k 10 900 python3 -m pytest tests -x -q -m gpu > $o/pytest_gpu.log 2>&1 || true
 tail -3 $o/pytest_gpu.log
-python3 bench.py > $o/bench_default.json 2> $o/bench_default.err
-python3 bench.py --steps 20 --warmup 5 > $o/bench_driver_like.json 2> $o/bench_driver_like.err
+python3 bench.py --full > $o/bench_default.json 2> $o/bench_default.err
+python3 bench.py --full --steps 20 --warmup 5 > $o/bench_driver_like.json 2> $o/bench_driver_like.err
 bash tools/pmc_run.sh $o/pmc > $o/pmc_run.log 2>&1 || true
 python3 - <<'PY'
 import json

@@ -5,12 +5,12 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 o=gpurun_out/r6_F2
 mkdir -p $o
 N="--no-cpu-baseline --no-sweep"
-python3 bench.py --workload encode --steps 4 > $o/bench_encode.json 2> $o/bench_encode.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof_encode -- python3 bench.py --workload encode --steps 2 --no-cpu-baseline > $o/bench_encode_profiled.json 2> $o/bench_encode_profiled.err
+python3 bench.py --full --workload encode --steps 4 > $o/bench_encode.json 2> $o/bench_encode.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof_encode -- python3 bench.py --full --workload encode --steps 2 --no-cpu-baseline > $o/bench_encode_profiled.json 2> $o/bench_encode_profiled.err
 python3 bench.py --workload cfg5 --steps 3 --warmup 1 $N > $o/bench_cfg5.json 2> $o/bench_cfg5.err
 python3 bench.py --workload cfg5r --steps 3 --warmup 1 $N > $o/bench_cfg5r.json 2> $o/bench_cfg5r.err
 python3 bench.py --workload cfg4 $N > $o/bench_cfg4.json 2> $o/bench_cfg4.err
-python3 bench.py --workload cfg1 --no-sweep > $o/bench_cfg1.json 2> $o/bench_cfg1.err
+python3 bench.py --full --workload cfg1 --no-sweep > $o/bench_cfg1.json 2> $o/bench_cfg1.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof_cfg2 -- python3 bench.py --steps 6 --warmup 2 $N --headline-parity off > $o/bench_cfg2_profiled.json 2> $o/bench_cfg2_profiled.err
 find $o -name "*kernel_trace.csv" -size +30M -delete
 R="--steps 2 --warmup 1 --no-cpu-baseline --no-sweep --headline-parity off"

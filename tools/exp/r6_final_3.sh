@@ -7,8 +7,8 @@ timeout -k 10 900 python3 -m pytest tests -x -q -m gpu > $o/pytest_gpu.log 2>&1 
 tail -3 $o/pytest_gpu.log
 python3 -c "import __graft_entry__ as g; g.smoke()" > $o/smoke.log 2>&1 || true
 tail -1 $o/smoke.log
-python3 bench.py > $o/bench_default.json 2> $o/bench_default.err
-python3 bench.py --workload encode --steps 4 > $o/bench_encode.json 2> $o/bench_encode.err
+python3 bench.py --full > $o/bench_default.json 2> $o/bench_default.err
+python3 bench.py --full --workload encode --steps 4 > $o/bench_encode.json 2> $o/bench_encode.err
 python3 - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r6_F3/bench_default.json").read().strip().split("\n")[-1])

@@ -7,7 +7,7 @@ mkdir -p $o
 N="--no-cpu-baseline --no-sweep"
 python3 bench.py --workload cfg4 $N > $o/bench_cfg4.json 2> $o/bench_cfg4.err
 echo cfg4 done
-python3 bench.py --workload cfg1 --no-sweep > $o/bench_cfg1.json 2> $o/bench_cfg1.err
+python3 bench.py --full --workload cfg1 --no-sweep > $o/bench_cfg1.json 2> $o/bench_cfg1.err
 echo cfg1 done
 python3 bench.py --workload cfg5 --steps 3 --warmup 1 $N > $o/bench_cfg5.json 2> $o/bench_cfg5.err
 echo cfg5 done
