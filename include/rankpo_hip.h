@@ -324,6 +324,51 @@ int rpo_lastq_attn_bwd(const void* q, int64_t q_stride, const void* k, const voi
                        void* dq, int64_t dq_stride, void* dk, void* dv, int64_t dk_stride, int64_t dv_stride, rpo_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * (9) packed forward of the BERT / XLM-R block (rankpo_amd/csrc/bert_ops.hip; BertEncoder.pooled_cls, used by
+ * ModelForInference.encode for CLS-pooled models: modeling.py:231-232, 473-554).  bf16 or fp16 storage (RPO_DT_F32 is
+ * RPO_ERR_UNSUPPORTED), f32 arithmetic, one rounding per stored value unless stated otherwise.
+ *
+ * rpo_bidir_attn_fwd: non-causal variable-length attention over packed tokens (replaces HF BertSelfAttention's
+ * softmax(Q K^T scale + mask) V, which the padded path runs as F.scaled_dot_product_attention with a boolean key mask:
+ * rankpo_amd/encoder.py BertAttention.forward).  q: [total_q, num_heads, head_dim], k / v: [T_k, num_heads, head_dim], token
+ * strides q_stride / k_stride / v_stride elements, heads contiguous (all three may be column blocks of ONE fused q|k|v
+ * projection output); out: [total_q, num_heads * head_dim] with token stride out_stride.  cu_seqlens_q / cu_seqlens_k: int32
+ * [N + 1], query rows and key rows of sequence n (one table for both is self-attention; cu_seqlens_q = 0, 1, .., N with
+ * cu_seqlens_k = the token table is one query per sequence, its CLS row).  tiles: the work list, int32 [ntiles][tile_cols]
+ * = (sequence id, first query row inside the sequence) with tile_cols == 2 and q_block == 32 query rows per entry (any other
+ * format: RPO_ERR_UNSUPPORTED); one wave per (entry, head).  Scores and the online softmax in f32, P rounded to the storage
+ * type for the PV product (as flash attention does), `scale` multiplies the scores.  lse (may be NULL): f32 [num_heads][total_q],
+ * natural log.  head_dim 32 or 64, num_heads == num_kv_heads; q / k / v 16-byte aligned with strides % 8 == 0, out 8-byte
+ * aligned with out_stride % 4 == 0.  Every sequence length >= 1 works.
+ *
+ * rpo_add_layernorm_fwd: y = LayerNorm(a + b) * gamma + beta (HF BertSelfOutput / BertOutput: `LayerNorm(dense(h) + input)`;
+ * b = the dense output with its bias already added by the GEMM epilogue, a = the residual).  a + b is rounded to the storage
+ * type first (the reference's own sum), mean / variance in f32 from it, y rounded once.  b may be NULL (LayerNorm of a).
+ * a, b, y: [rows, d] with row strides lda / ldb / ldy (the last block writes N CLS rows through them); gamma / beta [d].
+ * d % 8 == 0, d <= 4096, 16-byte aligned, strides % 8 == 0.
+ *
+ * rpo_gelu_fwd: x = x * 0.5 * (1 + erf(x / sqrt 2)) in place (HF BertIntermediate, hidden_act "gelu"), f32 inside, one
+ * rounding; x: [rows, cols], row stride ld; cols % 8 == 0, ld % 8 == 0, 16-byte aligned.
+ *
+ * rpo_bert_embed_ln_fwd: HF BertEmbeddings.forward on packed tokens: x = (word[ids] + type[token_types]) + pos_emb[pos], rounded
+ * to the storage type after each add as the reference's `inputs_embeds + token_type_embeddings; += position_embeddings`, then
+ * LayerNorm as above into y [tokens, d] (row stride ldy).  ids / pos / token_types: int32 [tokens]; token_types may be NULL
+ * (type 0 for every token).  Tables contiguous [vocab | n_types | n_pos, d]; an index outside its table is clamped into it
+ * (the caller checks the ranges).  Same d / alignment rules as rpo_add_layernorm_fwd.
+ * --------------------------------------------------------------------------------------------- */
+int rpo_bidir_attn_fwd(const void* q, const void* k, const void* v, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                       const int* cu_seqlens_q, const int* cu_seqlens_k, const int* tiles, int64_t ntiles, int64_t tile_cols,
+                       int64_t q_block, int64_t total_q, int64_t num_heads, int64_t num_kv_heads, int64_t head_dim, int dtype,
+                       float scale, void* out, int64_t out_stride, float* lse, rpo_stream_t stream);
+int rpo_add_layernorm_fwd(const void* a, int64_t lda, const void* b, int64_t ldb, const void* gamma, const void* beta, float eps,
+                          void* y, int64_t ldy, int64_t rows, int64_t d, int dtype, rpo_stream_t stream);
+int rpo_gelu_fwd(void* x, int64_t rows, int64_t cols, int64_t ld, int dtype, rpo_stream_t stream);
+int rpo_bert_embed_ln_fwd(const int* ids, const int* token_types, const int* pos, int64_t tokens, const void* word,
+                          int64_t vocab, const void* type_emb, int64_t n_types, const void* pos_emb, int64_t n_pos,
+                          const void* gamma, const void* beta, float eps, void* y, int64_t ldy, int64_t d, int dtype,
+                          rpo_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * (8) exact top-k over score rows, merged chunk by chunk ("next" row f3: the k-selection of faiss.IndexFlatIP.search,
  * reference src/utils.py:58-80).  scores: [rows, cols] (row stride ld elements) of the chunk whose first column is corpus
  * row col0; best_val f32 [rows, k] / best_idx int64 [rows, k]: the winners so far, best first (value descending, ties by

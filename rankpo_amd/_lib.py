@@ -78,6 +78,12 @@ SIGNATURES = {
     "rpo_lastq_attn_bwd": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _i64, _vp, _i64, _vp,
                                      _vp, _i64, _vp, _vp, _i64, _i64, _vp]),
     "rpo_rope": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _vp]),
+    "rpo_bidir_attn_fwd": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32,
+                                     _f32, _vp, _i64, _vp, _vp]),
+    "rpo_add_layernorm_fwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _f32, _vp, _i64, _i64, _i64, _i32, _vp]),
+    "rpo_gelu_fwd": (C.c_int, [_vp, _i64, _i64, _i64, _i32, _vp]),
+    "rpo_bert_embed_ln_fwd": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _f32, _vp, _i64, _i64, _i32,
+                                        _vp]),
 }
 
 _lib = None

@@ -830,6 +830,128 @@ class BertEncoder(nn.Module):
             x = checkpoint(layer, x, mask, use_reentrant=False) if ck else layer(x, mask)
         return EncoderOutput(last_hidden_state=x) if return_dict else (x,)
 
+    def native_decline_reason(self) -> Optional[str]:
+        """Why the packed HIP forward (`pooled_cls`) declines this model as it stands, or None if it takes it (the mask is
+        checked separately)."""
+        cfg, w = self.config, self.embeddings.word_embeddings.weight
+        d, nh = cfg.hidden_size, cfg.num_attention_heads
+        if not BERT_NATIVE:
+            return "BERT_NATIVE is off"
+        if torch.is_grad_enabled():
+            return "grad enabled"
+        if self.training and any(isinstance(m, nn.Dropout) and m.p > 0 for m in self.modules()):
+            return "training with dropout"     # dropout is not in the kernels (training is a later step)
+        if not _on_hip_device(w):
+            return "not on a HIP device"
+        if w.dtype not in (torch.bfloat16, torch.float16):
+            return "storage dtype"
+        if d % nh or d // nh not in _ops.BERT_HEAD_DIMS or d % 8 or d > 4096 or cfg.intermediate_size % 8:
+            return "shape"
+        if getattr(cfg, "hidden_act", "gelu") != "gelu":
+            return "activation"
+        return None
+
+    def pooled_cls(self, input_ids, attention_mask, token_type_ids=None):
+        """== forward(...).last_hidden_state[:, 0] (the CLS rows the reference pools, modeling.py:231-232) for 0/1 masks whose
+        first column is set, computed on packed tokens by the hand-written forward (bert_ops.hip): no pad token is computed,
+        attention is variable-length and non-causal, LayerNorm and GELU are fused kernels, and the LAST block computes K / V for
+        every token but Q, attention, the output dense, LayerNorm and FFN for the N CLS rows only.  Returns [N, d], or None to
+        decline (the caller then runs the padded forward): grad enabled, training with dropout, f32 / CPU model, head_dim
+        outside {32, 64}, a mask that is not 0/1, a row whose first token is masked, ids out of their tables, BERT_NATIVE off.
+        Host tensors (what a tokenizer returns) are checked and packed on the host and uploaded once: no device sync."""
+        if attention_mask is None or self.native_decline_reason() is not None:
+            return None
+        host = lambda t: None if t is None else t.cpu()           # device tensors: one sync here, as the padded path's mask check
+        cfg = self.config
+        packed = bert_pack(host(input_ids), host(attention_mask), host(token_type_ids),
+                           roberta=self.embeddings.roberta_positions, pad_id=self.embeddings.pad_id)
+        if packed is None:
+            return None
+        ids, pos, tts, lens = packed
+        emb = self.embeddings
+        if (int(ids.min()) < 0 or int(ids.max()) >= emb.word_embeddings.num_embeddings or int(pos.min()) < 0
+                or int(pos.max()) >= emb.position_embeddings.num_embeddings
+                or (tts is not None and (int(tts.min()) < 0 or int(tts.max()) >= emb.token_type_embeddings.num_embeddings))):
+            return None                        # the padded path raises for these, as HF does
+        N, T = len(lens), ids.shape[0]
+        d, nh = cfg.hidden_size, cfg.num_attention_heads
+        hd = d // nh
+        cu = torch.zeros(N + 1, dtype=torch.int64)
+        cu[1:] = torch.tensor(lens, dtype=torch.int64).cumsum(0)
+        tiles = torch.from_numpy(_ops.bidir_attn_tile_list(lens, lens)).reshape(-1)
+        tiles_cls = torch.from_numpy(_ops.bidir_attn_tile_list([1] * N, lens)).reshape(-1)
+        parts = [ids, pos] + ([tts] if tts is not None else []) + [cu, torch.arange(N + 1), tiles, tiles_cls]
+        dev = emb.word_embeddings.weight.device
+        buf = torch.cat([p.to(torch.int32) for p in parts]).pin_memory().to(dev, non_blocking=True)   # the one upload
+        views, o = [], 0
+        for p in parts:
+            views.append(buf[o:o + p.numel()])
+            o += p.numel()
+        ids_d, pos_d = views[0], views[1]
+        tts_d = views[2] if tts is not None else None
+        cu_d, cu_cls, tiles_d, tiles_cls_d = [t for t in views[-4:]]
+        tiles_d, tiles_cls_d = tiles_d.view(-1, 2), tiles_cls_d.view(-1, 2)
+        cls_idx = cu_d[:-1]                                       # the first packed token of every sequence is its CLS token
+        x = _ops.bert_embed_ln(ids_d, pos_d, tts_d, emb.word_embeddings.weight, emb.token_type_embeddings.weight,
+                               emb.position_embeddings.weight, emb.LayerNorm.weight, emb.LayerNorm.bias, emb.LayerNorm.eps)
+        scale = 1.0 / math.sqrt(hd)
+        layers = self.encoder.layer
+        if len(layers) == 0:
+            return x.index_select(0, cls_idx)
+        for i, layer in enumerate(layers):
+            att, so = layer.attention.self, layer.attention.output
+            if i < len(layers) - 1:
+                # q|k|v as ONE GEMM on the concatenated weights, built per call (never cached: a weight update is always seen)
+                qkv = F.linear(x, torch.cat([att.query.weight, att.key.weight, att.value.weight]),
+                               torch.cat([att.query.bias, att.key.bias, att.value.bias]))
+                q, k, v = (qkv[:, j * d:(j + 1) * d].view(T, nh, hd) for j in range(3))
+                o, _ = _ops.bidir_attn_fwd(q, k, v, cu_d, cu_d, tiles_d, scale)
+                res = x
+            else:
+                # last block: only the CLS rows are read downstream -- K / V for every token, the rest for N rows
+                kv = F.linear(x, torch.cat([att.key.weight, att.value.weight]), torch.cat([att.key.bias, att.value.bias]))
+                res = x.index_select(0, cls_idx)
+                q = F.linear(res, att.query.weight, att.query.bias)
+                o, _ = _ops.bidir_attn_fwd(q.view(N, nh, hd), kv[:, :d].view(T, nh, hd), kv[:, d:].view(T, nh, hd), cu_cls, cu_d,
+                                           tiles_cls_d, scale)
+            x = _ops.add_layernorm(res, F.linear(o, so.dense.weight, so.dense.bias), so.LayerNorm.weight, so.LayerNorm.bias,
+                                   so.LayerNorm.eps)
+            h = _ops.gelu_(F.linear(x, layer.intermediate.dense.weight, layer.intermediate.dense.bias))
+            out = layer.output
+            x = _ops.add_layernorm(x, F.linear(h, out.dense.weight, out.dense.bias), out.LayerNorm.weight, out.LayerNorm.bias,
+                                   out.LayerNorm.eps)
+        return x
+
+
+BERT_NATIVE = True       # BertEncoder.pooled_cls runs the packed hand-written forward; False: it declines and the padded PyTorch
+#                          path runs (the A/B arm of tools/bert_encode_bench.py)
+
+
+def _on_hip_device(t) -> bool:
+    return t.is_cuda
+
+
+def bert_pack(input_ids, attention_mask, token_type_ids=None, roberta: bool = False, pad_id=0):
+    """Host side of `BertEncoder.pooled_cls`: the tokens with mask == 1, row by row -> (ids, positions, token types or None,
+    lengths), int64, or None when the mask is not 0/1 or a row's first token is masked (HF then reads a pad token's row).
+    Position ids come from the PADDED layout with BertEmbeddings' own rules (BERT: the column; RoBERTa / XLM-R: the running
+    count of non-pad ids times keep + pad_id), so a mask with holes gives the rows of the padded path."""
+    m = attention_mask
+    if m.dim() != 2 or m.shape[1] == 0 or not bool(((m == 0) | (m == 1)).all()) or not bool((m[:, 0] == 1).all()):
+        return None
+    N, L = m.shape
+    if roberta:
+        keep = input_ids.ne(pad_id).to(torch.int64)
+        pos = torch.cumsum(keep, dim=1) * keep + pad_id
+    else:
+        pos = torch.arange(L, dtype=torch.int64).expand(N, L)
+    flat = torch.nonzero(m.reshape(-1).to(torch.bool), as_tuple=False).squeeze(1)
+    ids = input_ids.reshape(-1)[flat].to(torch.int64)
+    pos = pos.reshape(-1)[flat]
+    tts = None if token_type_ids is None else token_type_ids.reshape(-1)[flat].to(torch.int64)
+    lens = m.to(torch.int64).sum(1).tolist()
+    return ids, pos, tts, lens
+
 
 def disable_dropout_in_model(model: nn.Module) -> None:
     """trl.trainer.utils.disable_dropout_in_model, which the reference calls when `disable_dropout` is set

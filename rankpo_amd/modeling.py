@@ -318,6 +318,10 @@ class ModelForInference(nn.Module):
                 # right-padded batches (the tokenizer's default): packed tokens, no pad token is ever computed, the last
                 # block runs for the pooled rows only; None for any other mask.  The tensors are still on the host here.
                 pooled = self.model.pooled_last_token(inputs["input_ids"], inputs["attention_mask"])
+            elif mode == "cls" and hasattr(self.model, "pooled_cls"):
+                # BERT / XLM-R in 16-bit storage: the packed hand-written forward returns the CLS rows (host packing, no device
+                # sync); None for anything it declines, which then runs the padded forward below exactly as before
+                pooled = self.model.pooled_cls(inputs["input_ids"], inputs["attention_mask"])
             if pooled is not None:
                 emb = ops.pool_normalize(pooled[:, None, :], None, "cls", self.normalize_embeddings)
             else:

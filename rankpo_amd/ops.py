@@ -1107,6 +1107,93 @@ def last_query_attn(q, kv, cu, num_kv_heads: int, head_dim: int, scale: float):
 
 
 # ------------------------------------------------------------------------------------------------
+# (9) packed forward of the BERT / XLM-R block (BertEncoder.pooled_cls; no autograd: forward only)
+# ------------------------------------------------------------------------------------------------
+BIDIR_ATTN_Q_BLOCK = 32      # query rows per work-list entry of rpo_bidir_attn_fwd (the only format the kernel takes)
+BERT_HEAD_DIMS = (32, 64)
+
+
+def bidir_attn_tile_list(lens_q, lens_k, q_block: int = BIDIR_ATTN_Q_BLOCK):
+    """The work list of `bidir_attn_fwd` as a host numpy int32 [n, 2] = (sequence id, first query row): one entry per
+    (sequence, block of q_block queries), sequences with the most keys first (their entries are the longest-running ones)."""
+    import numpy as np
+    lq = np.asarray(lens_q, dtype=np.int64)
+    lk = np.asarray(lens_k, dtype=np.int64)
+    order = np.argsort(-lk, kind="stable")
+    nt = (lq[order] + q_block - 1) // q_block
+    seq = np.repeat(order, nt)
+    q0 = (np.arange(int(nt.sum())) - np.repeat(np.cumsum(nt) - nt, nt)) * q_block
+    return np.stack([seq, q0], 1).astype(np.int32).reshape(-1, 2)
+
+
+def bidir_attn_tile_table(lens_q, lens_k, device, q_block: int = BIDIR_ATTN_Q_BLOCK):
+    return torch.from_numpy(bidir_attn_tile_list(lens_q, lens_k, q_block)).to(device, non_blocking=True)
+
+
+def bidir_attn_fwd(q, k, v, cu_q, cu_k, tiles, scale, want_lse: bool = False):
+    """Non-causal variable-length attention: q [Tq, nh, hd], k / v [Tk, nh, hd] (heads contiguous, token stride free: column
+    blocks of one fused projection output), cu_q / cu_k int32 [N + 1], tiles from `bidir_attn_tile_table(lens_q, lens_k)`.
+    Returns (out [Tq, nh * hd], lse f32 [nh, Tq] or None)."""
+    lib = _lib.load()
+    Tq, nh, hd = q.shape
+    for t in (q, k, v):
+        if t.stride(2) != 1 or t.stride(1) != hd:
+            raise ValueError("bidir_attn_fwd: heads must be contiguous inside a token row")
+    out = torch.empty((Tq, nh * hd), dtype=q.dtype, device=q.device)
+    lse = torch.empty((nh, Tq), dtype=torch.float32, device=q.device) if want_lse else None
+    with torch.cuda.device(q.device):
+        check(lib.rpo_bidir_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(0), k.stride(0), v.stride(0),
+                                     cu_q.data_ptr(), cu_k.data_ptr(), tiles.data_ptr(), tiles.shape[0], tiles.shape[1],
+                                     BIDIR_ATTN_Q_BLOCK, Tq, nh, k.shape[1], hd, _dt(q), float(scale), out.data_ptr(), nh * hd,
+                                     _p(lse), _stream(q)), "rpo_bidir_attn_fwd")
+    return out, lse
+
+
+def add_layernorm(a, b, weight, bias, eps, out=None):
+    """LayerNorm(a + b) * weight + bias over the last dim of 2-D row-strided a / b (b may be None); a + b rounded to the storage
+    dtype first.  out: [rows, d] (row stride free) or None (a new contiguous tensor)."""
+    lib = _lib.load()
+    rows, d = a.shape
+    if out is None:
+        out = torch.empty((rows, d), dtype=a.dtype, device=a.device)
+    for t in (a, b, out):
+        if t is not None and t.stride(1) != 1:
+            raise ValueError("add_layernorm: rows must be contiguous")
+    with torch.cuda.device(a.device):
+        check(lib.rpo_add_layernorm_fwd(a.data_ptr(), a.stride(0), _p(b), b.stride(0) if b is not None else 0,
+                                        weight.data_ptr(), bias.data_ptr(), float(eps), out.data_ptr(), out.stride(0), rows, d,
+                                        _dt(a), _stream(a)), "rpo_add_layernorm_fwd")
+    return out
+
+
+def gelu_(x):
+    """Exact erf GELU in place over a 2-D row-strided x; returns x."""
+    lib = _lib.load()
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("gelu_: 2-D with contiguous rows")
+    with torch.cuda.device(x.device):
+        check(lib.rpo_gelu_fwd(x.data_ptr(), x.shape[0], x.shape[1], x.stride(0), _dt(x), _stream(x)), "rpo_gelu_fwd")
+    return x
+
+
+def bert_embed_ln(ids, pos, token_types, word, type_emb, pos_emb, weight, bias, eps):
+    """(word[ids] + type_emb[token_types]) + pos_emb[pos], then LayerNorm: ids / pos / token_types int32 [T] on the device
+    (token_types None: type 0) -> [T, d].  The caller checks the index ranges (the kernel clamps)."""
+    lib = _lib.load()
+    T, d = ids.shape[0], word.shape[1]
+    for t in (word, type_emb, pos_emb):
+        if not t.is_contiguous():
+            raise ValueError("bert_embed_ln: embedding tables must be contiguous")
+    out = torch.empty((T, d), dtype=word.dtype, device=word.device)
+    with torch.cuda.device(word.device):
+        check(lib.rpo_bert_embed_ln_fwd(ids.data_ptr(), _p(token_types), pos.data_ptr(), T, word.data_ptr(), word.shape[0],
+                                        type_emb.data_ptr(), type_emb.shape[0], pos_emb.data_ptr(), pos_emb.shape[0],
+                                        weight.data_ptr(), bias.data_ptr(), float(eps), out.data_ptr(), d, d, _dt(word),
+                                        _stream(word)), "rpo_bert_embed_ln_fwd")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # (8) exact top-k over score chunks (retrieval, "next" row f3)
 # ------------------------------------------------------------------------------------------------
 TOPK_MAX_K = 1024
