@@ -369,6 +369,72 @@ int rpo_bert_embed_ln_fwd(const int* ids, const int* token_types, const int* pos
                           rpo_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * (10) packed TRAINING step of the BERT / XLM-R block (rankpo_amd/csrc/bert_ops.hip; BertEncoder.pooled_cls_train, used by
+ * ModelForTraining.embed for CLS-pooled models).  bf16 or fp16 storage (RPO_DT_F32 is RPO_ERR_UNSUPPORTED), f32 arithmetic,
+ * no allocation, no host sync, no atomics: deterministic.  Shapes, strides, work lists and alignment as in section (9) unless
+ * stated otherwise.
+ *
+ * Attention-probability dropout: keep(seed, head, packed query row, packed key row) is one stateless counter-based function
+ * (Philox2x32-10; counter = (query row, key row >> 2), key = a 32-bit mix of seed and head; each key of a group of 4 reads its own
+ * 16-bit field and is kept when field >= round(p_drop * 65536)).  "Packed row" = the row index in q resp. k as passed to the call.
+ * 0 <= p_drop < 1; p_drop < 2^-17 takes the kernels without dropout.  The caller folds the layer index into `seed`.
+ *
+ * rpo_bidir_attn_train_fwd: rpo_bidir_attn_fwd with dropout.  The row sum and lse (required) come from the undropped
+ * probabilities P; out = (P o keep / (1 - p_drop)) V.
+ *
+ * rpo_bidir_attn_bwd: backward of either forward from q, k, v, out, dout, lse -> dq, dk, dv (each strided like its input: all
+ * may be column blocks of one fused buffer; 8-byte aligned, strides % 4 == 0; out / dout 16-byte aligned, strides % 8 == 0).
+ * Two launches: a dQ kernel, one wave per (q_tiles entry = 32 queries, head), looping over the sequence's keys, and a dK/dV
+ * kernel, one wave per (k_tiles entry = (sequence id, first key row inside the sequence), 32 keys, head), looping over the
+ * sequence's queries.  delta = rowsum(dout o out) in f32 inside both; P and dS are rounded to the storage type before their MFMA.
+ * dP <- keep o dP / (1 - p_drop), dS = P o (dP - delta), dV uses the dropped P.  Every row of dq / dk / dv that a work list covers
+ * is written; block_rows == 32, tile_cols == 2.
+ *
+ * rpo_bidir_attn_dropout_mask: mask[h][i][j] (uint8, 1 = kept) for heads head0 + h < head0 + num_heads, query rows q_row0 + i,
+ * key rows k_row0 + j of one sequence's block, from the same device function.  Tests and diagnostics only.
+ *
+ * rpo_add_layernorm_train_fwd / rpo_bert_embed_ln_train_fwd: the forward entries of section (9), bit for bit, which also store the
+ * rounded sum s [rows, d] (row stride lds) that the statistics are taken from.
+ *
+ * rpo_layernorm_bwd: from s, gamma and dy: mean / rstd recomputed per row in f32 as the forward takes them; ds = rstd (g - mean(g)
+ * - xhat mean(g xhat)), g = dy gamma, xhat = (s - mean) rstd: the gradient of BOTH addends.  dgamma_partial / dbeta_partial: f32
+ * [rpo_layernorm_bwd_blocks(rows), d], per-block sums of dy xhat / dy in a fixed order (four waves
+ * per block, one row per wave at a time, the waves' sums added in wave order); the caller adds the blocks.
+ *
+ * rpo_gelu_out_fwd: h = gelu(u) out of place (the arithmetic of rpo_gelu_fwd).  rpo_gelu_bwd: du = dh (Phi(u) + u phi(u)), exact
+ * erf form, one rounding.
+ * --------------------------------------------------------------------------------------------- */
+int rpo_bidir_attn_train_fwd(const void* q, const void* k, const void* v, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                             const int* cu_seqlens_q, const int* cu_seqlens_k, const int* tiles, int64_t ntiles,
+                             int64_t tile_cols, int64_t q_block, int64_t total_q, int64_t num_heads, int64_t num_kv_heads,
+                             int64_t head_dim, int dtype, float scale, float p_drop, uint64_t seed, void* out,
+                             int64_t out_stride, float* lse, rpo_stream_t stream);
+int rpo_bidir_attn_bwd(const void* q, const void* k, const void* v, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                       const void* out, int64_t out_stride, const void* dout, int64_t dout_stride, const float* lse,
+                       const int* cu_seqlens_q, const int* cu_seqlens_k, const int* q_tiles, int64_t n_q_tiles,
+                       const int* k_tiles, int64_t n_k_tiles, int64_t tile_cols, int64_t block_rows, int64_t total_q,
+                       int64_t num_heads, int64_t num_kv_heads, int64_t head_dim, int dtype, float scale, float p_drop,
+                       uint64_t seed, void* dq, int64_t dq_stride, void* dk, int64_t dk_stride, void* dv, int64_t dv_stride,
+                       rpo_stream_t stream);
+int rpo_bidir_attn_dropout_mask(int64_t q_row0, int64_t k_row0, int64_t len_q, int64_t len_k, int64_t head0, int64_t num_heads,
+                                float p_drop, uint64_t seed, unsigned char* mask, rpo_stream_t stream);
+int rpo_add_layernorm_train_fwd(const void* a, int64_t lda, const void* b, int64_t ldb, const void* gamma, const void* beta,
+                                float eps, void* y, int64_t ldy, void* s, int64_t lds, int64_t rows, int64_t d, int dtype,
+                                rpo_stream_t stream);
+int rpo_bert_embed_ln_train_fwd(const int* ids, const int* token_types, const int* pos, int64_t tokens, const void* word,
+                                int64_t vocab, const void* type_emb, int64_t n_types, const void* pos_emb, int64_t n_pos,
+                                const void* gamma, const void* beta, float eps, void* y, int64_t ldy, void* s, int64_t lds,
+                                int64_t d, int dtype, rpo_stream_t stream);
+int rpo_layernorm_bwd_blocks(int64_t rows);
+int rpo_layernorm_bwd(const void* s, int64_t lds, const void* gamma, const void* dy, int64_t lddy, float eps, void* ds,
+                      int64_t ldds, float* dgamma_partial, float* dbeta_partial, int64_t rows, int64_t d, int dtype,
+                      rpo_stream_t stream);
+int rpo_gelu_out_fwd(const void* u, int64_t ldu, void* h, int64_t ldh, int64_t rows, int64_t cols, int dtype,
+                     rpo_stream_t stream);
+int rpo_gelu_bwd(const void* u, int64_t ldu, const void* dh, int64_t lddh, void* du, int64_t lddu, int64_t rows, int64_t cols,
+                 int dtype, rpo_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * (8) exact top-k over score rows, merged chunk by chunk ("next" row f3: the k-selection of faiss.IndexFlatIP.search,
  * reference src/utils.py:58-80).  scores: [rows, cols] (row stride ld elements) of the chunk whose first column is corpus
  * row col0; best_val f32 [rows, k] / best_idx int64 [rows, k]: the winners so far, best first (value descending, ties by

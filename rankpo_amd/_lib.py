@@ -36,7 +36,7 @@ class RankPOHipError(RuntimeError):
     pass
 
 
-_vp, _i64, _i32, _f32, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_size_t
+_vp, _i64, _i32, _f32, _sz, _u64 = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_size_t, C.c_uint64
 
 # name -> (restype, argtypes); mirrors include/rankpo_hip.h one to one
 SIGNATURES = {
@@ -84,6 +84,19 @@ SIGNATURES = {
     "rpo_gelu_fwd": (C.c_int, [_vp, _i64, _i64, _i64, _i32, _vp]),
     "rpo_bert_embed_ln_fwd": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _f32, _vp, _i64, _i64, _i32,
                                         _vp]),
+    "rpo_bidir_attn_train_fwd": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                                           _i32, _f32, _f32, _u64, _vp, _i64, _vp, _vp]),
+    "rpo_bidir_attn_bwd": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64,
+                                     _i64, _i64, _i64, _i64, _i64, _i64, _i32, _f32, _f32, _u64, _vp, _i64, _vp, _i64, _vp, _i64,
+                                     _vp]),
+    "rpo_bidir_attn_dropout_mask": (C.c_int, [_i64, _i64, _i64, _i64, _i64, _i64, _f32, _u64, _vp, _vp]),
+    "rpo_add_layernorm_train_fwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _f32, _vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp]),
+    "rpo_bert_embed_ln_train_fwd": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _f32, _vp, _i64, _vp,
+                                              _i64, _i64, _i32, _vp]),
+    "rpo_layernorm_bwd_blocks": (C.c_int, [_i64]),
+    "rpo_layernorm_bwd": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _f32, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp]),
+    "rpo_gelu_out_fwd": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp]),
+    "rpo_gelu_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp]),
 }
 
 _lib = None

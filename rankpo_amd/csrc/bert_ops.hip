@@ -6,7 +6,14 @@
 //   rpo_add_layernorm_fwd  LayerNorm(a + b) (HF BertSelfOutput / BertOutput: `LayerNorm(dropout(dense(h)) + input)`)
 //   rpo_gelu_fwd           exact erf GELU in place (HF BertIntermediate with hidden_act "gelu")
 //   rpo_bert_embed_ln_fwd  word + token type + position embedding gather, then LayerNorm (HF BertEmbeddings.forward)
-// Plain HIP with MFMA builtins; no inline asm, no counted waits.
+// and the TRAINING step on the same packed layout (`BertEncoder.pooled_cls_train`):
+//   rpo_bidir_attn_train_fwd     the forward with attention-probability dropout (a template arm of the same kernel)
+//   rpo_bidir_attn_bwd           dQ kernel + dK/dV kernel in the forward's wave layout, P recomputed from lse, dropout replayed
+//   rpo_bidir_attn_dropout_mask  the keep mask of a block from the kernels' own device function (tests, diagnostics)
+//   rpo_add_layernorm_train_fwd / rpo_bert_embed_ln_train_fwd   the forwards, also storing the rounded sum s
+//   rpo_layernorm_bwd            ds and per-block dgamma / dbeta partials from s, gamma and dy
+//   rpo_gelu_out_fwd / rpo_gelu_bwd   out-of-place GELU and its derivative
+// Plain HIP with MFMA builtins; no inline asm, no counted waits.  No atomics: every entry is deterministic.
 #include "common.hpp"
 
 namespace {
@@ -47,11 +54,64 @@ constexpr int kAttnQBlock = 32;     // queries per work-list entry
 constexpr int kAttnKeys = 32;       // keys per step
 constexpr float kLn2 = 0.6931471805599453f;
 
-template <typename T, int HD>
+// ---- attention-probability dropout ---------------------------------------------------------------
+// keep(seed, head, packed query row, packed key row): ONE stateless counter-based function shared by the training forward, both
+// backward kernels and the mask dump.  Philox2x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11) with
+// counter = (packed query row, packed key row >> 2) and a 32-bit key mixed (murmur3 finaliser) from the 64-bit seed and the head;
+// the 64 output bits are four 16-bit fields, one per key of the group of 4, and a key is KEPT when its field >= thr =
+// round(p_drop * 65536) (p_drop is quantised to 1 / 65536).  dropout_keep is that function; dropout_keep4 and the dK/dV kernel
+// evaluate the same pieces (dropout_key, dropout_bits, dropout_field_keep) with the shared parts hoisted.
+__device__ __forceinline__ unsigned fmix32(unsigned x) {
+    x ^= x >> 16;
+    x *= 0x85ebca6bu;
+    x ^= x >> 13;
+    x *= 0xc2b2ae35u;
+    return x ^ (x >> 16);
+}
+struct DropBits { unsigned c0, c1; };
+__device__ __forceinline__ unsigned dropout_key(uint64_t seed, int head) {
+    return fmix32((unsigned)seed ^ fmix32((unsigned)(seed >> 32) ^ fmix32((unsigned)head + 0x9e3779b9u)));
+}
+__device__ __forceinline__ DropBits dropout_bits(unsigned key, int qrow, int kgroup) {
+    unsigned c0 = (unsigned)qrow, c1 = (unsigned)kgroup;
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const unsigned hi = __umulhi(0xd256d193u, c0), lo = 0xd256d193u * c0;
+        c0 = hi ^ key ^ c1;
+        c1 = lo;
+        key += 0x9e3779b9u;
+    }
+    return DropBits{c0, c1};
+}
+__device__ __forceinline__ bool dropout_field_keep(DropBits b, int krow, unsigned thr) {
+    return ((((krow & 2) ? b.c1 : b.c0) >> (16 * (krow & 1))) & 0xffffu) >= thr;
+}
+__device__ __forceinline__ bool dropout_keep(uint64_t seed, int head, int qrow, int krow, unsigned thr) {
+    return dropout_field_keep(dropout_bits(dropout_key(seed, head), qrow, krow >> 2), krow, thr);
+}
+// dropout_keep for the four consecutive key rows krow0 .. krow0 + 3 of one query row (what a lane of the forward and of the dQ
+// kernel owns): they lie in one group of 4 when krow0 is a multiple of 4 (wave-uniform: the sequence's first packed row decides
+// it), else in two, so one or two Philox evaluations serve four elements.  key = dropout_key(seed, head).
+__device__ __forceinline__ void dropout_keep4(unsigned key, int qrow, int krow0, unsigned thr, bool (&keep)[4]) {
+    const DropBits lo = dropout_bits(key, qrow, krow0 >> 2);
+    if ((krow0 & 3) == 0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) keep[i] = dropout_field_keep(lo, krow0 + i, thr);
+    } else {
+        const DropBits hi = dropout_bits(key, qrow, (krow0 >> 2) + 1);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) keep[i] = dropout_field_keep(((krow0 + i) >> 2) == (krow0 >> 2) ? lo : hi, krow0 + i, thr);
+    }
+}
+
+// DROP: the training arm (rpo_bidir_attn_train_fwd).  The row sum and lse come from the undropped probabilities; dropped ones
+// enter the PV product as zeros and O is scaled by inv_keep = 1 / (1 - p_drop) at the end.  DROP = false is the forward as before.
+template <typename T, int HD, bool DROP>
 __global__ __launch_bounds__(64) void bidir_attn_fwd_kernel(
     const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, int64_t q_stride, int64_t k_stride,
     int64_t v_stride, const int* __restrict__ cu_q, const int* __restrict__ cu_k, const int* __restrict__ tiles,
-    float scale_log2, T* __restrict__ out, int64_t out_stride, float* __restrict__ lse, int64_t total_q) {
+    float scale_log2, T* __restrict__ out, int64_t out_stride, float* __restrict__ lse, int64_t total_q, unsigned thr,
+    float inv_keep, uint64_t seed) {
     constexpr int QS = kAttnQBlock / 16;   // query tiles per wave
     constexpr int KS = HD / 32;            // k-steps of the score product
     constexpr int OB = HD / 16;            // 16-row blocks of O^T
@@ -143,6 +203,12 @@ __global__ __launch_bounds__(64) void bidir_attn_fwd_kernel(
                     p[i] = __builtin_amdgcn_exp2f(sc[b][s][i] - mn);
                     ps += p[i];
                 }
+                if constexpr (DROP) {
+                    bool keep[4];
+                    dropout_keep4(dropout_key(seed, h), tq0 + q0 + s * 16 + r, tk0 + kt + b * 16 + 4 * g, thr, keep);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) p[i] = keep[i] ? p[i] : 0.f;
+                }
                 w[2 * b] = pack2<T>(p[0], p[1]);
                 w[2 * b + 1] = pack2<T>(p[2], p[3]);
             }
@@ -174,7 +240,8 @@ __global__ __launch_bounds__(64) void bidir_attn_fwd_kernel(
         L += __shfl_xor(L, 32, 64);
         const int qi = q0 + s * 16 + r;
         if (qi >= lq) continue;
-        const float inv = L > 0.f ? 1.0f / L : 0.f;
+        float inv = L > 0.f ? 1.0f / L : 0.f;
+        if constexpr (DROP) inv *= inv_keep;
         T* op = out + (int64_t)(tq0 + qi) * out_stride + hcol + 4 * g;
 #pragma unroll
         for (int b = 0; b < OB; ++b) {
@@ -182,6 +249,347 @@ __global__ __launch_bounds__(64) void bidir_attn_fwd_kernel(
             *reinterpret_cast<uint2_t*>(op + 16 * b) = pk;
         }
         if (lse && g == 0) lse[(int64_t)h * total_q + tq0 + qi] = L > 0.f ? (m[s] + log2f(L)) * kLn2 : -INFINITY;
+    }
+}
+
+// ---- (1b) backward of the bidirectional attention -------------------------------------------------
+// Two launches in the forward's wave layout.  P is recomputed from lse, delta = rowsum(dO o O) is computed in f32 in both kernels,
+// P and dS are rounded to the storage type before they enter an MFMA (as the forward rounds P).  With dropout, dP <- keep o dP /
+// (1 - p), dS = P o (dP - delta), and dV uses the dropped P.
+//
+// dQ: one wave per (32-query entry, head), loop over the sequence's keys.  S^T = K Q^T and dP^T = V dO^T land in the forward's
+// accumulator layout (lane: query l & 15, keys 4 g + i of each 16-key half), dS^T is the B operand of dQ^T = K^T dS^T as it lies in
+// the registers, K is staged row-major in LDS and read column-wise (the forward's V path).
+template <typename T, int HD, bool DROP>
+__global__ __launch_bounds__(64) void bidir_attn_bwd_dq_kernel(
+    const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, int64_t q_stride, int64_t k_stride,
+    int64_t v_stride, const T* __restrict__ out, int64_t out_stride, const T* __restrict__ dout, int64_t dout_stride,
+    const float* __restrict__ lse, const int* __restrict__ cu_q, const int* __restrict__ cu_k, const int* __restrict__ tiles,
+    float scale, float scale_log2, T* __restrict__ dq, int64_t dq_stride, int64_t total_q, unsigned thr, float inv_keep,
+    uint64_t seed) {
+    constexpr int QS = kAttnQBlock / 16;
+    constexpr int KS = HD / 32;
+    constexpr int OB = HD / 16;
+    constexpr int VLD = HD + 8;
+    constexpr int VCH = kAttnKeys * HD / 8 / 64;
+    __shared__ __attribute__((aligned(16))) unsigned short ksm[kAttnKeys * VLD];
+
+    const int entry = blockIdx.x, h = blockIdx.y;
+    const int seq = tiles[2 * entry], q0 = tiles[2 * entry + 1];
+    const int tq0 = cu_q[seq], lq = cu_q[seq + 1] - tq0;
+    const int tk0 = cu_k[seq], lk = cu_k[seq + 1] - tk0;
+    const int lane = threadIdx.x, r = lane & 15, g = lane >> 4;
+    const int64_t hcol = (int64_t)h * HD;
+    if (lq <= 0) return;
+
+    uint4_t qf[QS][KS], dof[QS][KS];
+    float nl[QS], delta[QS];
+#pragma unroll
+    for (int s = 0; s < QS; ++s) {
+        const int qi = min(q0 + s * 16 + r, lq - 1);     // rows past the end: loaded (in bounds), never stored
+        const T* qp = q + (int64_t)(tq0 + qi) * q_stride + hcol + 8 * g;
+        const T* dop = dout + (int64_t)(tq0 + qi) * dout_stride + hcol + 8 * g;
+        const T* op = out + (int64_t)(tq0 + qi) * out_stride + hcol + 8 * g;
+        float dl = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            qf[s][ks] = *reinterpret_cast<const uint4_t*>(qp + 32 * ks);
+            dof[s][ks] = *reinterpret_cast<const uint4_t*>(dop + 32 * ks);
+            Vec16<T> a, b;
+            a.load(dop + 32 * ks);
+            b.load(op + 32 * ks);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) dl = fmaf(a.v[e], b.v[e], dl);
+        }
+        dl += __shfl_xor(dl, 16, 64);
+        dl += __shfl_xor(dl, 32, 64);
+        delta[s] = dl;
+        nl[s] = -lse[(int64_t)h * total_q + tq0 + qi] * 1.4426950408889634f;
+    }
+    float4_t acc[QS][OB];
+#pragma unroll
+    for (int s = 0; s < QS; ++s)
+#pragma unroll
+        for (int b = 0; b < OB; ++b) acc[s][b] = float4_t{0.f, 0.f, 0.f, 0.f};
+
+    for (int kt = 0; kt < lk; kt += kAttnKeys) {
+        uint4_t kr[VCH];
+#pragma unroll
+        for (int c = 0; c < VCH; ++c) {
+            const int idx = lane + 64 * c, key = idx / (HD / 8), c8 = idx - key * (HD / 8);
+            const int kk = min(kt + key, lk - 1);
+            kr[c] = *reinterpret_cast<const uint4_t*>(k + (int64_t)(tk0 + kk) * k_stride + hcol + 8 * c8);
+        }
+        float4_t sc[2][QS], dp[2][QS];
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int kk = min(kt + b * 16 + r, lk - 1);
+            const T* kp = k + (int64_t)(tk0 + kk) * k_stride + hcol + 8 * g;
+            const T* vp = v + (int64_t)(tk0 + kk) * v_stride + hcol + 8 * g;
+            uint4_t kf[KS], vf[KS];
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                kf[ks] = *reinterpret_cast<const uint4_t*>(kp + 32 * ks);
+                vf[ks] = *reinterpret_cast<const uint4_t*>(vp + 32 * ks);
+            }
+#pragma unroll
+            for (int s = 0; s < QS; ++s) {
+                sc[b][s] = float4_t{0.f, 0.f, 0.f, 0.f};
+                dp[b][s] = float4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) {
+                    AttnMma<T>::mma(kf[ks], qf[s][ks], sc[b][s]);
+                    AttnMma<T>::mma(vf[ks], dof[s][ks], dp[b][s]);
+                }
+            }
+        }
+        __syncthreads();                                   // the previous step's K reads are done
+#pragma unroll
+        for (int c = 0; c < VCH; ++c) {
+            const int idx = lane + 64 * c, key = idx / (HD / 8), c8 = idx - key * (HD / 8);
+            *reinterpret_cast<uint4_t*>(&ksm[key * VLD + 8 * c8]) = kr[c];
+        }
+        // dS^T[key kt + 16 b + 4 g + i][query q0 + 16 s + r] = P (dP - delta); masked keys: P = 0
+        uint4_t dsf[QS];
+#pragma unroll
+        for (int s = 0; s < QS; ++s) {
+            unsigned w[4];
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                float ds[4];
+                bool keep[4] = {true, true, true, true};
+                if constexpr (DROP) dropout_keep4(dropout_key(seed, h), tq0 + q0 + s * 16 + r, tk0 + kt + b * 16 + 4 * g, thr, keep);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int key = kt + b * 16 + 4 * g + i;
+                    const float p = key < lk ? __builtin_amdgcn_exp2f(fmaf(sc[b][s][i], scale_log2, nl[s])) : 0.f;
+                    float d = dp[b][s][i];
+                    if constexpr (DROP) d = keep[i] ? d * inv_keep : 0.f;
+                    ds[i] = p * (d - delta[s]);
+                }
+                w[2 * b] = pack2<T>(ds[0], ds[1]);
+                w[2 * b + 1] = pack2<T>(ds[2], ds[3]);
+            }
+            dsf[s] = uint4_t{w[0], w[1], w[2], w[3]};
+        }
+        __syncthreads();                                   // K tile visible
+        // A = K^T (row = head dim 16 b + r, k slot j = key 4 g + j for j < 4, 16 + 4 g + j - 4 else), B = dS^T
+#pragma unroll
+        for (int b = 0; b < OB; ++b) {
+            unsigned e[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int key = (j < 4) ? 4 * g + j : 16 + 4 * g + (j - 4);
+                e[j] = ksm[key * VLD + 16 * b + r];
+            }
+            const uint4_t ka{e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16)};
+#pragma unroll
+            for (int s = 0; s < QS; ++s) AttnMma<T>::mma(ka, dsf[s], acc[s][b]);
+        }
+    }
+
+#pragma unroll
+    for (int s = 0; s < QS; ++s) {
+        const int qi = q0 + s * 16 + r;
+        if (qi >= lq) continue;
+        T* op = dq + (int64_t)(tq0 + qi) * dq_stride + hcol + 4 * g;
+#pragma unroll
+        for (int b = 0; b < OB; ++b) {
+            const uint2_t pk{pack2<T>(acc[s][b][0] * scale, acc[s][b][1] * scale), pack2<T>(acc[s][b][2] * scale, acc[s][b][3] * scale)};
+            *reinterpret_cast<uint2_t*>(op + 16 * b) = pk;
+        }
+    }
+}
+
+// dK / dV: one wave per (32-key entry, head), loop over the sequence's queries in steps of 32.  The roles of the forward swap: the
+// wave keeps its keys' K and V as B operands, S = Q K^T and dP = dO V^T take 16 query rows straight from global memory as A, so
+// every lane owns ONE key (column l & 15) and queries 4 g + i of each 16-query half.  The dropped P and dS are the B operands of
+// dV^T = dO^T P and dK^T = Q^T dS as they lie in the registers; Q and dO are staged row-major in LDS and read column-wise.
+// The step's delta values are computed by lane pairs (query lane >> 1, half of the head dim each) and passed through LDS.
+template <typename T, int HD, bool DROP>
+__global__ __launch_bounds__(64) void bidir_attn_bwd_dkv_kernel(
+    const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, int64_t q_stride, int64_t k_stride,
+    int64_t v_stride, const T* __restrict__ out, int64_t out_stride, const T* __restrict__ dout, int64_t dout_stride,
+    const float* __restrict__ lse, const int* __restrict__ cu_q, const int* __restrict__ cu_k, const int* __restrict__ tiles,
+    float scale, float scale_log2, T* __restrict__ dk, int64_t dk_stride, T* __restrict__ dv, int64_t dv_stride, int64_t total_q,
+    unsigned thr, float inv_keep, uint64_t seed) {
+    constexpr int KT = kAttnQBlock / 16;   // key tiles per wave
+    constexpr int KS = HD / 32;
+    constexpr int OB = HD / 16;
+    constexpr int VLD = HD + 8;
+    constexpr int VCH = kAttnKeys * HD / 8 / 64;
+    __shared__ __attribute__((aligned(16))) unsigned short qsm[kAttnKeys * VLD];
+    __shared__ __attribute__((aligned(16))) unsigned short dosm[kAttnKeys * VLD];
+    __shared__ float dlsm[kAttnKeys];
+
+    const int entry = blockIdx.x, h = blockIdx.y;
+    const int seq = tiles[2 * entry], k0 = tiles[2 * entry + 1];
+    const int tq0 = cu_q[seq], lq = cu_q[seq + 1] - tq0;
+    const int tk0 = cu_k[seq], lk = cu_k[seq + 1] - tk0;
+    const int lane = threadIdx.x, r = lane & 15, g = lane >> 4;
+    const int64_t hcol = (int64_t)h * HD;
+    if (lk <= 0) return;
+
+    uint4_t kf[KT][KS], vf[KT][KS];
+#pragma unroll
+    for (int s = 0; s < KT; ++s) {
+        const int ki = min(k0 + s * 16 + r, lk - 1);     // rows past the end: loaded (in bounds), never stored
+        const T* kp = k + (int64_t)(tk0 + ki) * k_stride + hcol + 8 * g;
+        const T* vp = v + (int64_t)(tk0 + ki) * v_stride + hcol + 8 * g;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            kf[s][ks] = *reinterpret_cast<const uint4_t*>(kp + 32 * ks);
+            vf[s][ks] = *reinterpret_cast<const uint4_t*>(vp + 32 * ks);
+        }
+    }
+    float4_t dka[KT][OB], dva[KT][OB];
+#pragma unroll
+    for (int s = 0; s < KT; ++s)
+#pragma unroll
+        for (int b = 0; b < OB; ++b) {
+            dka[s][b] = float4_t{0.f, 0.f, 0.f, 0.f};
+            dva[s][b] = float4_t{0.f, 0.f, 0.f, 0.f};
+        }
+
+    for (int qt = 0; qt < lq; qt += kAttnKeys) {
+        uint4_t qr[VCH], dor[VCH];
+#pragma unroll
+        for (int c = 0; c < VCH; ++c) {
+            const int idx = lane + 64 * c, row = idx / (HD / 8), c8 = idx - row * (HD / 8);
+            const int qq = min(qt + row, lq - 1);
+            qr[c] = *reinterpret_cast<const uint4_t*>(q + (int64_t)(tq0 + qq) * q_stride + hcol + 8 * c8);
+            dor[c] = *reinterpret_cast<const uint4_t*>(dout + (int64_t)(tq0 + qq) * dout_stride + hcol + 8 * c8);
+        }
+        float dl = 0.f;
+        {
+            const int qq = min(qt + (lane >> 1), lq - 1);
+            const T* dop = dout + (int64_t)(tq0 + qq) * dout_stride + hcol + (lane & 1) * (HD / 2);
+            const T* op = out + (int64_t)(tq0 + qq) * out_stride + hcol + (lane & 1) * (HD / 2);
+#pragma unroll
+            for (int c = 0; c < HD / 16; ++c) {
+                Vec16<T> a, b;
+                a.load(dop + 8 * c);
+                b.load(op + 8 * c);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) dl = fmaf(a.v[e], b.v[e], dl);
+            }
+            dl += __shfl_xor(dl, 1, 64);
+        }
+        float4_t sc[2][KT], dp[2][KT];
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int qq = min(qt + b * 16 + r, lq - 1);
+            const T* qp = q + (int64_t)(tq0 + qq) * q_stride + hcol + 8 * g;
+            const T* dop = dout + (int64_t)(tq0 + qq) * dout_stride + hcol + 8 * g;
+            uint4_t qa[KS], da[KS];
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                qa[ks] = *reinterpret_cast<const uint4_t*>(qp + 32 * ks);
+                da[ks] = *reinterpret_cast<const uint4_t*>(dop + 32 * ks);
+            }
+#pragma unroll
+            for (int s = 0; s < KT; ++s) {
+                sc[b][s] = float4_t{0.f, 0.f, 0.f, 0.f};
+                dp[b][s] = float4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) {
+                    AttnMma<T>::mma(qa[ks], kf[s][ks], sc[b][s]);
+                    AttnMma<T>::mma(da[ks], vf[s][ks], dp[b][s]);
+                }
+            }
+        }
+        __syncthreads();                                   // the previous step's LDS reads are done
+#pragma unroll
+        for (int c = 0; c < VCH; ++c) {
+            const int idx = lane + 64 * c, row = idx / (HD / 8), c8 = idx - row * (HD / 8);
+            *reinterpret_cast<uint4_t*>(&qsm[row * VLD + 8 * c8]) = qr[c];
+            *reinterpret_cast<uint4_t*>(&dosm[row * VLD + 8 * c8]) = dor[c];
+        }
+        if ((lane & 1) == 0) dlsm[lane >> 1] = dl;
+        __syncthreads();                                   // Q, dO tiles and delta visible
+        // element [query qt + 16 b + 4 g + i][key k0 + 16 s + r]; queries past the end: P = 0
+        float nl[2][4], de[2][4];
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int qq = min(qt + b * 16 + 4 * g + i, lq - 1);
+                nl[b][i] = -lse[(int64_t)h * total_q + tq0 + qq] * 1.4426950408889634f;
+                de[b][i] = dlsm[b * 16 + 4 * g + i];
+            }
+        uint4_t pf[KT], dsf[KT];
+#pragma unroll
+        for (int s = 0; s < KT; ++s) {
+            unsigned wp[4], wd[4];
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                float p[4], ds[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int qq = qt + b * 16 + 4 * g + i;
+                    const float pu = qq < lq ? __builtin_amdgcn_exp2f(fmaf(sc[b][s][i], scale_log2, nl[b][i])) : 0.f;
+                    float d = dp[b][s][i];
+                    p[i] = pu;
+                    if constexpr (DROP) {
+                        const int krow = tk0 + k0 + s * 16 + r;     // one key, four queries per lane: one evaluation per element
+                        const bool keep = dropout_field_keep(dropout_bits(dropout_key(seed, h), tq0 + qq, krow >> 2), krow, thr);
+                        d = keep ? d * inv_keep : 0.f;
+                        p[i] = keep ? pu : 0.f;
+                    }
+                    ds[i] = pu * (d - de[b][i]);
+                }
+                wp[2 * b] = pack2<T>(p[0], p[1]);
+                wp[2 * b + 1] = pack2<T>(p[2], p[3]);
+                wd[2 * b] = pack2<T>(ds[0], ds[1]);
+                wd[2 * b + 1] = pack2<T>(ds[2], ds[3]);
+            }
+            pf[s] = uint4_t{wp[0], wp[1], wp[2], wp[3]};
+            dsf[s] = uint4_t{wd[0], wd[1], wd[2], wd[3]};
+        }
+        // A = dO^T / Q^T (row = head dim 16 b + r, k slot j = query 4 g + j for j < 4, 16 + 4 g + j - 4 else), B = P / dS
+#pragma unroll
+        for (int b = 0; b < OB; ++b) {
+            unsigned e[8], f[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int row = (j < 4) ? 4 * g + j : 16 + 4 * g + (j - 4);
+                e[j] = dosm[row * VLD + 16 * b + r];
+                f[j] = qsm[row * VLD + 16 * b + r];
+            }
+            const uint4_t da{e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16)};
+            const uint4_t qa{f[0] | (f[1] << 16), f[2] | (f[3] << 16), f[4] | (f[5] << 16), f[6] | (f[7] << 16)};
+#pragma unroll
+            for (int s = 0; s < KT; ++s) {
+                AttnMma<T>::mma(da, pf[s], dva[s][b]);
+                AttnMma<T>::mma(qa, dsf[s], dka[s][b]);
+            }
+        }
+    }
+
+    const float vscale = DROP ? inv_keep : 1.0f;
+#pragma unroll
+    for (int s = 0; s < KT; ++s) {
+        const int ki = k0 + s * 16 + r;
+        if (ki >= lk) continue;
+        T* kp = dk + (int64_t)(tk0 + ki) * dk_stride + hcol + 4 * g;
+        T* vp = dv + (int64_t)(tk0 + ki) * dv_stride + hcol + 4 * g;
+#pragma unroll
+        for (int b = 0; b < OB; ++b) {
+            const uint2_t pk{pack2<T>(dka[s][b][0] * scale, dka[s][b][1] * scale), pack2<T>(dka[s][b][2] * scale, dka[s][b][3] * scale)};
+            const uint2_t pv{pack2<T>(dva[s][b][0] * vscale, dva[s][b][1] * vscale), pack2<T>(dva[s][b][2] * vscale, dva[s][b][3] * vscale)};
+            *reinterpret_cast<uint2_t*>(kp + 16 * b) = pk;
+            *reinterpret_cast<uint2_t*>(vp + 16 * b) = pv;
+        }
+    }
+}
+
+// the keep mask of one sequence's block, heads head0 .. head0 + nh - 1: mask[head][query][key] (tests and diagnostics)
+__global__ __launch_bounds__(256) void dropout_mask_kernel(int q_row0, int k_row0, int lq, int lk, int head0, int nh, unsigned thr,
+                                                           uint64_t seed, unsigned char* __restrict__ mask) {
+    const int64_t n = (int64_t)nh * lq * lk;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int key = (int)(i % lk), qi = (int)((i / lk) % lq), hh = (int)(i / ((int64_t)lk * lq));
+        mask[i] = dropout_keep(seed, head0 + hh, q_row0 + qi, k_row0 + key, thr) ? 1 : 0;
     }
 }
 
@@ -227,7 +635,8 @@ template <typename T, int NV>
 __global__ __launch_bounds__(kRowThreads) void add_layernorm_kernel(const T* __restrict__ a, int64_t lda, const T* __restrict__ b,
                                                                      int64_t ldb, const T* __restrict__ gamma,
                                                                      const T* __restrict__ beta, float eps, T* __restrict__ y,
-                                                                     int64_t ldy, int64_t rows, int d) {
+                                                                     int64_t ldy, T* __restrict__ s_out, int64_t lds,
+                                                                     int64_t rows, int d) {
     const int64_t row = (int64_t)blockIdx.x * (kRowThreads / 64) + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= rows) return;
@@ -243,6 +652,7 @@ __global__ __launch_bounds__(kRowThreads) void add_layernorm_kernel(const T* __r
 #pragma unroll
                 for (int e = 0; e < 8; ++e) x[j].v[e] = Elem<T>::round(x[j].v[e] + t.v[e]);   // the reference's rounded sum
             }
+            if (s_out) x[j].store(s_out + row * lds + c0);   // training: the backward recomputes the statistics from it
         }
     }
     layernorm_store<T, NV>(x, gamma, beta, eps, y + row * ldy, d, lane);
@@ -252,7 +662,8 @@ template <typename T, int NV>
 __global__ __launch_bounds__(kRowThreads) void bert_embed_ln_kernel(
     const int* __restrict__ ids, const int* __restrict__ tts, const int* __restrict__ pos, int64_t tokens,
     const T* __restrict__ word, int64_t vocab, const T* __restrict__ temb, int64_t ntypes, const T* __restrict__ pemb,
-    int64_t npos, const T* __restrict__ gamma, const T* __restrict__ beta, float eps, T* __restrict__ y, int64_t ldy, int d) {
+    int64_t npos, const T* __restrict__ gamma, const T* __restrict__ beta, float eps, T* __restrict__ y, int64_t ldy, T* __restrict__ s_out,
+    int64_t lds, int d) {
     const int64_t row = (int64_t)blockIdx.x * (kRowThreads / 64) + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= tokens) return;
@@ -272,6 +683,7 @@ __global__ __launch_bounds__(kRowThreads) void bert_embed_ln_kernel(
             p.load(pemb + pi * d + c0);
 #pragma unroll
             for (int e = 0; e < 8; ++e) x[j].v[e] = Elem<T>::round(Elem<T>::round(x[j].v[e] + t.v[e]) + p.v[e]);   // (w + t) + p
+            if (s_out) x[j].store(s_out + row * lds + c0);
         }
     }
     layernorm_store<T, NV>(x, gamma, beta, eps, y + row * ldy, d, lane);
@@ -288,6 +700,144 @@ __global__ __launch_bounds__(256) void gelu_kernel(T* __restrict__ x, int64_t ro
 #pragma unroll
         for (int e = 0; e < 8; ++e) t.v[e] = 0.5f * t.v[e] * (1.0f + erff(t.v[e] * 0.70710678118654752f));
         t.store(p);
+    }
+}
+
+// backward of LayerNorm(s) gamma + beta from the stored rounded sum s: mean / rstd recomputed per row in f32 exactly as the forward
+// takes them, ds = rstd (g - mean(g) - xhat mean(g xhat)) with g = dy gamma, xhat = (s - mean) rstd.  One wave per row, four waves
+// per block; wave w of block b walks rows 4 b + w, + 4 gridDim.x, .. with the row in registers and adds dy xhat / dy into per-lane
+// f32 sums in that fixed order; the block's four waves then add their sums through LDS in wave order 0, 1, 2, 3 and the last one
+// writes dgamma_partial / dbeta_partial [gridDim.x, d], summed by the caller (the dw_partial pattern of rpo_add_rmsnorm_bwd).
+constexpr int kLnBwdMaxBlocks = 1024;
+constexpr int kLnBwdWaves = 4;
+
+template <typename T, int NV>
+__global__ __launch_bounds__(64 * kLnBwdWaves) void layernorm_bwd_kernel(const T* __restrict__ s, int64_t lds, const T* __restrict__ gamma,
+                                                           const T* __restrict__ dy, int64_t lddy, float eps, T* __restrict__ ds,
+                                                           int64_t ldds, float* __restrict__ dgp, float* __restrict__ dbp,
+                                                           int64_t rows, int d) {
+    extern __shared__ float ln_red[];       // [2][d]: the block's dgamma | dbeta sums
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float dg[NV][8], db[NV][8];
+    Vec16<T> gw[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dg[j][e] = db[j][e] = 0.f;
+        if (8 * (lane + 64 * j) < d) gw[j].load(gamma + 8 * (lane + 64 * j));
+    }
+    for (int64_t row = (int64_t)blockIdx.x * kLnBwdWaves + wave; row < rows; row += (int64_t)gridDim.x * kLnBwdWaves) {
+        Vec16<T> x[NV], g[NV];
+        float sum = 0.f;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int c0 = 8 * (lane + 64 * j);
+            if (c0 < d) {
+                x[j].load(s + row * lds + c0);
+                g[j].load(dy + row * lddy + c0);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) sum += x[j].v[e];
+            }
+        }
+        const float mean = wave_sum(sum) / (float)d;
+        float sq = 0.f;
+#pragma unroll
+        for (int j = 0; j < NV; ++j)
+            if (8 * (lane + 64 * j) < d)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float c = x[j].v[e] - mean;
+                    sq = fmaf(c, c, sq);
+                }
+        const float rstd = rsqrtf(wave_sum(sq) / (float)d + eps);
+        float c1 = 0.f, c2 = 0.f;
+#pragma unroll
+        for (int j = 0; j < NV; ++j)
+            if (8 * (lane + 64 * j) < d)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float xh = (x[j].v[e] - mean) * rstd, dyv = g[j].v[e], gg = dyv * gw[j].v[e];
+                    dg[j][e] = fmaf(dyv, xh, dg[j][e]);
+                    db[j][e] += dyv;
+                    x[j].v[e] = xh;
+                    g[j].v[e] = gg;
+                    c1 += gg;
+                    c2 = fmaf(gg, xh, c2);
+                }
+        c1 = wave_sum(c1) / (float)d;
+        c2 = wave_sum(c2) / (float)d;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int c0 = 8 * (lane + 64 * j);
+            if (c0 < d) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) g[j].v[e] = rstd * (g[j].v[e] - c1 - x[j].v[e] * c2);
+                g[j].store(ds + row * ldds + c0);
+            }
+        }
+    }
+    for (int w = 0; w < kLnBwdWaves; ++w) {
+        if (wave == w) {
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+                const int c0 = 8 * (lane + 64 * j);
+                if (c0 < d) {
+                    float* gl = ln_red + c0;
+                    float* bl = ln_red + d + c0;
+                    float* gp = dgp + (int64_t)blockIdx.x * d + c0;
+                    float* bp = dbp + (int64_t)blockIdx.x * d + c0;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const float a = w == 0 ? dg[j][e] : gl[e] + dg[j][e];
+                        const float b = w == 0 ? db[j][e] : bl[e] + db[j][e];
+                        if (w == kLnBwdWaves - 1) {
+                            gp[e] = a;
+                            bp[e] = b;
+                        } else {
+                            gl[e] = a;
+                            bl[e] = b;
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// h = gelu(u) out of place: the pre-activation survives for the backward
+template <typename T>
+__global__ __launch_bounds__(256) void gelu_out_kernel(const T* __restrict__ u, int64_t ldu, T* __restrict__ hh, int64_t ldh,
+                                                       int64_t rows, int64_t cols) {
+    const int64_t vpr = cols / 8, n = rows * vpr;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t rr = i / vpr, c = (i - rr * vpr) * 8;
+        Vec16<T> t;
+        t.load(u + rr * ldu + c);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) t.v[e] = 0.5f * t.v[e] * (1.0f + erff(t.v[e] * 0.70710678118654752f));
+        t.store(hh + rr * ldh + c);
+    }
+}
+
+// du = dh (Phi(u) + u phi(u)): Phi = erfc(-u / sqrt 2) / 2 (no cancellation in the left tail), phi = exp(-u^2 / 2) / sqrt(2 pi)
+template <typename T>
+__global__ __launch_bounds__(256) void gelu_bwd_kernel(const T* __restrict__ u, int64_t ldu, const T* __restrict__ dh, int64_t lddh,
+                                                       T* __restrict__ du, int64_t lddu, int64_t rows, int64_t cols) {
+    const int64_t vpr = cols / 8, n = rows * vpr;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t rr = i / vpr, c = (i - rr * vpr) * 8;
+        Vec16<T> t, gvec;
+        t.load(u + rr * ldu + c);
+        gvec.load(dh + rr * lddh + c);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float x = t.v[e];
+            const float cdf = 0.5f * erfcf(-x * 0.70710678118654752f);
+            const float pdf = 0.3989422804014327f * __expf(-0.5f * x * x);
+            t.v[e] = gvec.v[e] * fmaf(x, pdf, cdf);
+        }
+        t.store(du + rr * lddu + c);
     }
 }
 
@@ -326,8 +876,8 @@ extern "C" int rpo_bidir_attn_fwd(const void* q, const void* k, const void* v, i
     hipStream_t st = (hipStream_t)stream;
     const float sl = scale * 1.4426950408889634f;
 #define RPO_BIDIR(T, HD)                                                                                                         \
-    RPO_LAUNCH((bidir_attn_fwd_kernel<T, HD>), grid, block, 0, st, (const T*)q, (const T*)k, (const T*)v, q_stride, k_stride, \
-               v_stride, cu_seqlens_q, cu_seqlens_k, tiles, sl, (T*)out, out_stride, lse, total_q)
+    RPO_LAUNCH((bidir_attn_fwd_kernel<T, HD, false>), grid, block, 0, st, (const T*)q, (const T*)k, (const T*)v, q_stride,      \
+               k_stride, v_stride, cu_seqlens_q, cu_seqlens_k, tiles, sl, (T*)out, out_stride, lse, total_q, 0u, 1.0f, (uint64_t)0)
     if (dtype == RPO_DT_BF16) {
         if (head_dim == 32) RPO_BIDIR(bf16_t, 32);
         else RPO_BIDIR(bf16_t, 64);
@@ -353,10 +903,10 @@ extern "C" int rpo_add_layernorm_fwd(const void* a, int64_t lda, const void* b, 
     hipStream_t st = (hipStream_t)stream;
     if (dtype == RPO_DT_BF16)
         RPO_ROW_DISPATCH(add_layernorm_kernel, bf16_t, nv, grid, st, (const bf16_t*)a, lda, (const bf16_t*)b, ldb,
-                         (const bf16_t*)gamma, (const bf16_t*)beta, eps, (bf16_t*)y, ldy, rows, (int)d);
+                         (const bf16_t*)gamma, (const bf16_t*)beta, eps, (bf16_t*)y, ldy, (bf16_t*)nullptr, (int64_t)0, rows, (int)d);
     else
         RPO_ROW_DISPATCH(add_layernorm_kernel, f16_t, nv, grid, st, (const f16_t*)a, lda, (const f16_t*)b, ldb,
-                         (const f16_t*)gamma, (const f16_t*)beta, eps, (f16_t*)y, ldy, rows, (int)d);
+                         (const f16_t*)gamma, (const f16_t*)beta, eps, (f16_t*)y, ldy, (f16_t*)nullptr, (int64_t)0, rows, (int)d);
     return rpo_launch_status();
 }
 
@@ -390,10 +940,267 @@ extern "C" int rpo_bert_embed_ln_fwd(const int* ids, const int* token_types, con
     if (dtype == RPO_DT_BF16)
         RPO_ROW_DISPATCH(bert_embed_ln_kernel, bf16_t, nv, grid, st, ids, token_types, pos, tokens, (const bf16_t*)word, vocab,
                          (const bf16_t*)type_emb, n_types, (const bf16_t*)pos_emb, n_pos, (const bf16_t*)gamma,
-                         (const bf16_t*)beta, eps, (bf16_t*)y, ldy, (int)d);
+                         (const bf16_t*)beta, eps, (bf16_t*)y, ldy, (bf16_t*)nullptr, (int64_t)0, (int)d);
     else
         RPO_ROW_DISPATCH(bert_embed_ln_kernel, f16_t, nv, grid, st, ids, token_types, pos, tokens, (const f16_t*)word, vocab,
                          (const f16_t*)type_emb, n_types, (const f16_t*)pos_emb, n_pos, (const f16_t*)gamma,
-                         (const f16_t*)beta, eps, (f16_t*)y, ldy, (int)d);
+                         (const f16_t*)beta, eps, (f16_t*)y, ldy, (f16_t*)nullptr, (int64_t)0, (int)d);
+    return rpo_launch_status();
+}
+
+// ---- training entries ---------------------------------------------------------------------------------
+namespace {
+bool attn_common_ok(int64_t num_heads, int64_t num_kv_heads, int64_t head_dim, int dtype, int64_t tile_cols, int64_t block,
+                    int64_t ntiles) {
+    return !(dtype == RPO_DT_F32 || (head_dim != 32 && head_dim != 64) || num_heads != num_kv_heads || tile_cols != 2 ||
+             block != kAttnQBlock || ntiles > 0x7fffffff || num_heads > 65535);
+}
+bool dropout_args(float p_drop, unsigned* thr, float* inv_keep) {      // false: p_drop outside [0, 1)
+    if (!(p_drop >= 0.f) || !(p_drop < 1.f)) return false;
+    *thr = (unsigned)lrintf(p_drop * 65536.f);
+    *inv_keep = 1.0f / (1.0f - p_drop);
+    return true;
+}
+}  // namespace
+
+#define RPO_ATTN_DISPATCH(LAUNCH)                           \
+    do {                                                    \
+        if (dtype == RPO_DT_BF16) {                         \
+            if (head_dim == 32) LAUNCH(bf16_t, 32);         \
+            else LAUNCH(bf16_t, 64);                        \
+        } else {                                            \
+            if (head_dim == 32) LAUNCH(f16_t, 32);          \
+            else LAUNCH(f16_t, 64);                         \
+        }                                                   \
+    } while (0)
+
+extern "C" int rpo_bidir_attn_train_fwd(const void* q, const void* k, const void* v, int64_t q_stride, int64_t k_stride,
+                                        int64_t v_stride, const int* cu_seqlens_q, const int* cu_seqlens_k, const int* tiles,
+                                        int64_t ntiles, int64_t tile_cols, int64_t q_block, int64_t total_q, int64_t num_heads,
+                                        int64_t num_kv_heads, int64_t head_dim, int dtype, float scale, float p_drop,
+                                        uint64_t seed, void* out, int64_t out_stride, float* lse, rpo_stream_t stream) {
+    unsigned thr;
+    float inv_keep;
+    if (!q || !k || !v || !cu_seqlens_q || !cu_seqlens_k || !tiles || !out || !lse || ntiles < 0 || total_q <= 0 ||
+        num_heads <= 0 || num_kv_heads <= 0 || head_dim <= 0 || !rpo_dtype_ok(dtype) || q_stride <= 0 || k_stride <= 0 ||
+        v_stride <= 0 || out_stride <= 0 || !dropout_args(p_drop, &thr, &inv_keep))
+        return RPO_ERR_INVALID_ARG;
+    if (!attn_common_ok(num_heads, num_kv_heads, head_dim, dtype, tile_cols, q_block, ntiles)) return RPO_ERR_UNSUPPORTED;
+    if (!rpo_aligned16(q) || !rpo_aligned16(k) || !rpo_aligned16(v) || (reinterpret_cast<uintptr_t>(out) & 7) || q_stride % 8 ||
+        k_stride % 8 || v_stride % 8 || out_stride % 4)
+        return RPO_ERR_UNSUPPORTED;
+    if (ntiles == 0) return RPO_OK;
+    const dim3 grid((unsigned)ntiles, (unsigned)num_heads), block(64);
+    hipStream_t st = (hipStream_t)stream;
+    const float sl = scale * 1.4426950408889634f;
+    const bool drop = thr > 0;
+#define RPO_BIDIR_T(T, HD)                                                                                                       \
+    do {                                                                                                                         \
+        if (drop)                                                                                                                \
+            RPO_LAUNCH((bidir_attn_fwd_kernel<T, HD, true>), grid, block, 0, st, (const T*)q, (const T*)k, (const T*)v,          \
+                       q_stride, k_stride, v_stride, cu_seqlens_q, cu_seqlens_k, tiles, sl, (T*)out, out_stride, lse, total_q,   \
+                       thr, inv_keep, seed);                                                                                     \
+        else                                                                                                                     \
+            RPO_LAUNCH((bidir_attn_fwd_kernel<T, HD, false>), grid, block, 0, st, (const T*)q, (const T*)k, (const T*)v,         \
+                       q_stride, k_stride, v_stride, cu_seqlens_q, cu_seqlens_k, tiles, sl, (T*)out, out_stride, lse, total_q,   \
+                       0u, 1.0f, (uint64_t)0);                                                                                   \
+    } while (0)
+    RPO_ATTN_DISPATCH(RPO_BIDIR_T);
+#undef RPO_BIDIR_T
+    return rpo_launch_status();
+}
+
+extern "C" int rpo_bidir_attn_bwd(const void* q, const void* k, const void* v, int64_t q_stride, int64_t k_stride,
+                                  int64_t v_stride, const void* out, int64_t out_stride, const void* dout, int64_t dout_stride,
+                                  const float* lse, const int* cu_seqlens_q, const int* cu_seqlens_k, const int* q_tiles,
+                                  int64_t n_q_tiles, const int* k_tiles, int64_t n_k_tiles, int64_t tile_cols, int64_t block_rows,
+                                  int64_t total_q, int64_t num_heads, int64_t num_kv_heads, int64_t head_dim, int dtype,
+                                  float scale, float p_drop, uint64_t seed, void* dq, int64_t dq_stride, void* dk,
+                                  int64_t dk_stride, void* dv, int64_t dv_stride, rpo_stream_t stream) {
+    unsigned thr;
+    float inv_keep;
+    if (!q || !k || !v || !out || !dout || !lse || !cu_seqlens_q || !cu_seqlens_k || !q_tiles || !k_tiles || !dq || !dk || !dv ||
+        n_q_tiles < 0 || n_k_tiles < 0 || total_q <= 0 || num_heads <= 0 || num_kv_heads <= 0 || head_dim <= 0 ||
+        !rpo_dtype_ok(dtype) || q_stride <= 0 || k_stride <= 0 || v_stride <= 0 || out_stride <= 0 || dout_stride <= 0 ||
+        dq_stride <= 0 || dk_stride <= 0 || dv_stride <= 0 || !dropout_args(p_drop, &thr, &inv_keep))
+        return RPO_ERR_INVALID_ARG;
+    if (!attn_common_ok(num_heads, num_kv_heads, head_dim, dtype, tile_cols, block_rows, n_q_tiles) || n_k_tiles > 0x7fffffff)
+        return RPO_ERR_UNSUPPORTED;
+    if (!rpo_aligned16(q) || !rpo_aligned16(k) || !rpo_aligned16(v) || !rpo_aligned16(out) || !rpo_aligned16(dout) ||
+        (reinterpret_cast<uintptr_t>(dq) & 7) || (reinterpret_cast<uintptr_t>(dk) & 7) || (reinterpret_cast<uintptr_t>(dv) & 7) ||
+        q_stride % 8 || k_stride % 8 || v_stride % 8 || out_stride % 8 || dout_stride % 8 || dq_stride % 4 || dk_stride % 4 ||
+        dv_stride % 4)
+        return RPO_ERR_UNSUPPORTED;
+    const dim3 block(64);
+    hipStream_t st = (hipStream_t)stream;
+    const float sl = scale * 1.4426950408889634f;
+    const bool drop = thr > 0;
+#define RPO_BIDIR_DQ(T, HD)                                                                                                      \
+    do {                                                                                                                         \
+        if (drop)                                                                                                                \
+            RPO_LAUNCH((bidir_attn_bwd_dq_kernel<T, HD, true>), grid, block, 0, st, (const T*)q, (const T*)k, (const T*)v,       \
+                       q_stride, k_stride, v_stride, (const T*)out, out_stride, (const T*)dout, dout_stride, lse, cu_seqlens_q,  \
+                       cu_seqlens_k, q_tiles, scale, sl, (T*)dq, dq_stride, total_q, thr, inv_keep, seed);                       \
+        else                                                                                                                     \
+            RPO_LAUNCH((bidir_attn_bwd_dq_kernel<T, HD, false>), grid, block, 0, st, (const T*)q, (const T*)k, (const T*)v,      \
+                       q_stride, k_stride, v_stride, (const T*)out, out_stride, (const T*)dout, dout_stride, lse, cu_seqlens_q,  \
+                       cu_seqlens_k, q_tiles, scale, sl, (T*)dq, dq_stride, total_q, 0u, 1.0f, (uint64_t)0);                     \
+    } while (0)
+#define RPO_BIDIR_DKV(T, HD)                                                                                                     \
+    do {                                                                                                                         \
+        if (drop)                                                                                                                \
+            RPO_LAUNCH((bidir_attn_bwd_dkv_kernel<T, HD, true>), grid, block, 0, st, (const T*)q, (const T*)k, (const T*)v,      \
+                       q_stride, k_stride, v_stride, (const T*)out, out_stride, (const T*)dout, dout_stride, lse, cu_seqlens_q,  \
+                       cu_seqlens_k, k_tiles, scale, sl, (T*)dk, dk_stride, (T*)dv, dv_stride, total_q, thr, inv_keep, seed);    \
+        else                                                                                                                     \
+            RPO_LAUNCH((bidir_attn_bwd_dkv_kernel<T, HD, false>), grid, block, 0, st, (const T*)q, (const T*)k, (const T*)v,     \
+                       q_stride, k_stride, v_stride, (const T*)out, out_stride, (const T*)dout, dout_stride, lse, cu_seqlens_q,  \
+                       cu_seqlens_k, k_tiles, scale, sl, (T*)dk, dk_stride, (T*)dv, dv_stride, total_q, 0u, 1.0f, (uint64_t)0);  \
+    } while (0)
+    if (n_q_tiles > 0) {
+        const dim3 grid((unsigned)n_q_tiles, (unsigned)num_heads);
+        RPO_ATTN_DISPATCH(RPO_BIDIR_DQ);
+        const int rc = rpo_launch_status();
+        if (rc != RPO_OK) return rc;
+    }
+    if (n_k_tiles > 0) {
+        const dim3 grid((unsigned)n_k_tiles, (unsigned)num_heads);
+        RPO_ATTN_DISPATCH(RPO_BIDIR_DKV);
+        return rpo_launch_status();
+    }
+#undef RPO_BIDIR_DQ
+#undef RPO_BIDIR_DKV
+    return RPO_OK;
+}
+
+extern "C" int rpo_bidir_attn_dropout_mask(int64_t q_row0, int64_t k_row0, int64_t len_q, int64_t len_k, int64_t head0,
+                                           int64_t num_heads, float p_drop, uint64_t seed, unsigned char* mask,
+                                           rpo_stream_t stream) {
+    unsigned thr;
+    float inv_keep;
+    if (!mask || q_row0 < 0 || k_row0 < 0 || len_q < 0 || len_k < 0 || head0 < 0 || num_heads < 0 ||
+        q_row0 + len_q > 0x7fffffff || k_row0 + len_k > 0x7fffffff || head0 + num_heads > 65535 ||
+        !dropout_args(p_drop, &thr, &inv_keep))
+        return RPO_ERR_INVALID_ARG;
+    const int64_t n = num_heads * len_q * len_k;
+    if (n == 0) return RPO_OK;
+    const int64_t nb = rpo_cdiv(n, 256);
+    RPO_LAUNCH(dropout_mask_kernel, dim3((unsigned)(nb < 65536 ? nb : 65536)), dim3(256), 0, (hipStream_t)stream, (int)q_row0,
+               (int)k_row0, (int)len_q, (int)len_k, (int)head0, (int)num_heads, thr, seed, mask);
+    return rpo_launch_status();
+}
+
+extern "C" int rpo_add_layernorm_train_fwd(const void* a, int64_t lda, const void* b, int64_t ldb, const void* gamma,
+                                           const void* beta, float eps, void* y, int64_t ldy, void* s, int64_t lds, int64_t rows,
+                                           int64_t d, int dtype, rpo_stream_t stream) {
+    if (!a || !gamma || !beta || !y || !s || rows < 0 || d <= 0 || !rpo_dtype_ok(dtype) || lda < d || ldy < d || lds < d ||
+        (b && ldb < d))
+        return RPO_ERR_INVALID_ARG;
+    const int nv = row_vectors(d);
+    if (dtype == RPO_DT_F32 || d % 8 || nv == 0) return RPO_ERR_UNSUPPORTED;
+    if (!rpo_aligned16(a) || (b && !rpo_aligned16(b)) || !rpo_aligned16(gamma) || !rpo_aligned16(beta) || !rpo_aligned16(y) ||
+        !rpo_aligned16(s) || lda % 8 || (b && ldb % 8) || ldy % 8 || lds % 8)
+        return RPO_ERR_UNSUPPORTED;
+    if (rows == 0) return RPO_OK;
+    const dim3 grid((unsigned)rpo_cdiv(rows, kRowThreads / 64));
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == RPO_DT_BF16)
+        RPO_ROW_DISPATCH(add_layernorm_kernel, bf16_t, nv, grid, st, (const bf16_t*)a, lda, (const bf16_t*)b, ldb,
+                         (const bf16_t*)gamma, (const bf16_t*)beta, eps, (bf16_t*)y, ldy, (bf16_t*)s, lds, rows, (int)d);
+    else
+        RPO_ROW_DISPATCH(add_layernorm_kernel, f16_t, nv, grid, st, (const f16_t*)a, lda, (const f16_t*)b, ldb,
+                         (const f16_t*)gamma, (const f16_t*)beta, eps, (f16_t*)y, ldy, (f16_t*)s, lds, rows, (int)d);
+    return rpo_launch_status();
+}
+
+extern "C" int rpo_bert_embed_ln_train_fwd(const int* ids, const int* token_types, const int* pos, int64_t tokens,
+                                           const void* word, int64_t vocab, const void* type_emb, int64_t n_types,
+                                           const void* pos_emb, int64_t n_pos, const void* gamma, const void* beta, float eps,
+                                           void* y, int64_t ldy, void* s, int64_t lds, int64_t d, int dtype, rpo_stream_t stream) {
+    if (!ids || !pos || !word || !type_emb || !pos_emb || !gamma || !beta || !y || !s || tokens < 0 || vocab <= 0 ||
+        n_types <= 0 || n_pos <= 0 || d <= 0 || ldy < d || lds < d || !rpo_dtype_ok(dtype))
+        return RPO_ERR_INVALID_ARG;
+    const int nv = row_vectors(d);
+    if (dtype == RPO_DT_F32 || d % 8 || nv == 0 || ldy % 8 || lds % 8) return RPO_ERR_UNSUPPORTED;
+    if (!rpo_aligned16(word) || !rpo_aligned16(type_emb) || !rpo_aligned16(pos_emb) || !rpo_aligned16(gamma) ||
+        !rpo_aligned16(beta) || !rpo_aligned16(y) || !rpo_aligned16(s))
+        return RPO_ERR_UNSUPPORTED;
+    if (tokens == 0) return RPO_OK;
+    const dim3 grid((unsigned)rpo_cdiv(tokens, kRowThreads / 64));
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == RPO_DT_BF16)
+        RPO_ROW_DISPATCH(bert_embed_ln_kernel, bf16_t, nv, grid, st, ids, token_types, pos, tokens, (const bf16_t*)word, vocab,
+                         (const bf16_t*)type_emb, n_types, (const bf16_t*)pos_emb, n_pos, (const bf16_t*)gamma,
+                         (const bf16_t*)beta, eps, (bf16_t*)y, ldy, (bf16_t*)s, lds, (int)d);
+    else
+        RPO_ROW_DISPATCH(bert_embed_ln_kernel, f16_t, nv, grid, st, ids, token_types, pos, tokens, (const f16_t*)word, vocab,
+                         (const f16_t*)type_emb, n_types, (const f16_t*)pos_emb, n_pos, (const f16_t*)gamma,
+                         (const f16_t*)beta, eps, (f16_t*)y, ldy, (f16_t*)s, lds, (int)d);
+    return rpo_launch_status();
+}
+
+extern "C" int rpo_layernorm_bwd_blocks(int64_t rows) {
+    const int64_t nb = rpo_cdiv(rows < 1 ? 1 : rows, kLnBwdWaves);
+    return (int)(nb < kLnBwdMaxBlocks ? nb : kLnBwdMaxBlocks);
+}
+
+extern "C" int rpo_layernorm_bwd(const void* s, int64_t lds, const void* gamma, const void* dy, int64_t lddy, float eps, void* ds,
+                                 int64_t ldds, float* dgamma_partial, float* dbeta_partial, int64_t rows, int64_t d, int dtype,
+                                 rpo_stream_t stream) {
+    if (!s || !gamma || !dy || !ds || !dgamma_partial || !dbeta_partial || rows <= 0 || d <= 0 || !rpo_dtype_ok(dtype) ||
+        lds < d || lddy < d || ldds < d)
+        return RPO_ERR_INVALID_ARG;
+    const int nv = row_vectors(d);
+    if (dtype == RPO_DT_F32 || d % 8 || nv == 0) return RPO_ERR_UNSUPPORTED;
+    if (!rpo_aligned16(s) || !rpo_aligned16(gamma) || !rpo_aligned16(dy) || !rpo_aligned16(ds) || lds % 8 || lddy % 8 || ldds % 8)
+        return RPO_ERR_UNSUPPORTED;
+    const dim3 grid((unsigned)rpo_layernorm_bwd_blocks(rows)), block(64 * kLnBwdWaves);
+    const size_t red_bytes = 2 * (size_t)d * sizeof(float);     // <= 32 KiB (d <= 4096)
+    hipStream_t st = (hipStream_t)stream;
+#define RPO_LN_BWD(T, NV)                                                                                                   \
+    RPO_LAUNCH((layernorm_bwd_kernel<T, NV>), grid, block, red_bytes, st, (const T*)s, lds, (const T*)gamma, (const T*)dy, lddy, eps, \
+               (T*)ds, ldds, dgamma_partial, dbeta_partial, rows, (int)d)
+#define RPO_LN_BWD_T(T)                  \
+    do {                                 \
+        if (nv == 1) RPO_LN_BWD(T, 1);   \
+        else if (nv == 2) RPO_LN_BWD(T, 2); \
+        else if (nv == 4) RPO_LN_BWD(T, 4); \
+        else RPO_LN_BWD(T, 8);           \
+    } while (0)
+    if (dtype == RPO_DT_BF16) RPO_LN_BWD_T(bf16_t);
+    else RPO_LN_BWD_T(f16_t);
+#undef RPO_LN_BWD_T
+#undef RPO_LN_BWD
+    return rpo_launch_status();
+}
+
+extern "C" int rpo_gelu_out_fwd(const void* u, int64_t ldu, void* h, int64_t ldh, int64_t rows, int64_t cols, int dtype,
+                                rpo_stream_t stream) {
+    if (!u || !h || rows < 0 || cols <= 0 || ldu < cols || ldh < cols || !rpo_dtype_ok(dtype)) return RPO_ERR_INVALID_ARG;
+    if (dtype == RPO_DT_F32 || cols % 8 || ldu % 8 || ldh % 8 || !rpo_aligned16(u) || !rpo_aligned16(h)) return RPO_ERR_UNSUPPORTED;
+    if (rows == 0) return RPO_OK;
+    const int64_t n = rows * (cols / 8), nb = rpo_cdiv(n, 256);
+    const dim3 grid((unsigned)(nb < 8192 ? nb : 8192)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == RPO_DT_BF16) RPO_LAUNCH(gelu_out_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)u, ldu, (bf16_t*)h, ldh, rows, cols);
+    else RPO_LAUNCH(gelu_out_kernel<f16_t>, grid, block, 0, st, (const f16_t*)u, ldu, (f16_t*)h, ldh, rows, cols);
+    return rpo_launch_status();
+}
+
+extern "C" int rpo_gelu_bwd(const void* u, int64_t ldu, const void* dh, int64_t lddh, void* du, int64_t lddu, int64_t rows,
+                            int64_t cols, int dtype, rpo_stream_t stream) {
+    if (!u || !dh || !du || rows < 0 || cols <= 0 || ldu < cols || lddh < cols || lddu < cols || !rpo_dtype_ok(dtype))
+        return RPO_ERR_INVALID_ARG;
+    if (dtype == RPO_DT_F32 || cols % 8 || ldu % 8 || lddh % 8 || lddu % 8 || !rpo_aligned16(u) || !rpo_aligned16(dh) ||
+        !rpo_aligned16(du))
+        return RPO_ERR_UNSUPPORTED;
+    if (rows == 0) return RPO_OK;
+    const int64_t n = rows * (cols / 8), nb = rpo_cdiv(n, 256);
+    const dim3 grid((unsigned)(nb < 8192 ? nb : 8192)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == RPO_DT_BF16)
+        RPO_LAUNCH(gelu_bwd_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)u, ldu, (const bf16_t*)dh, lddh, (bf16_t*)du, lddu, rows, cols);
+    else
+        RPO_LAUNCH(gelu_bwd_kernel<f16_t>, grid, block, 0, st, (const f16_t*)u, ldu, (const f16_t*)dh, lddh, (f16_t*)du, lddu, rows, cols);
     return rpo_launch_status();
 }

@@ -795,6 +795,7 @@ class BertEncoder(nn.Module):
         self.embeddings = BertEmbeddings(config)
         self.encoder = _BertStack(config)
         self.gradient_checkpointing = False
+        self.last_dropout_seed = None          # attention-dropout seed of the latest `pooled_cls_train` call (tests read it)
         self.apply(self._init)
 
     def _init(self, m):
@@ -851,18 +852,11 @@ class BertEncoder(nn.Module):
             return "activation"
         return None
 
-    def pooled_cls(self, input_ids, attention_mask, token_type_ids=None):
-        """== forward(...).last_hidden_state[:, 0] (the CLS rows the reference pools, modeling.py:231-232) for 0/1 masks whose
-        first column is set, computed on packed tokens by the hand-written forward (bert_ops.hip): no pad token is computed,
-        attention is variable-length and non-causal, LayerNorm and GELU are fused kernels, and the LAST block computes K / V for
-        every token but Q, attention, the output dense, LayerNorm and FFN for the N CLS rows only.  Returns [N, d], or None to
-        decline (the caller then runs the padded forward): grad enabled, training with dropout, f32 / CPU model, head_dim
-        outside {32, 64}, a mask that is not 0/1, a row whose first token is masked, ids out of their tables, BERT_NATIVE off.
-        Host tensors (what a tokenizer returns) are checked and packed on the host and uploaded once: no device sync."""
-        if attention_mask is None or self.native_decline_reason() is not None:
-            return None
+    def _pack_upload(self, input_ids, attention_mask, token_type_ids=None, train: bool = False):
+        """Host side shared by `pooled_cls` and `pooled_cls_train`: check and pack the batch (`bert_pack`), check the ids against
+        their tables, build the work lists and upload everything as ONE pinned int32 buffer.  None: decline.  train: also the
+        key-side work lists of the attention backward."""
         host = lambda t: None if t is None else t.cpu()           # device tensors: one sync here, as the padded path's mask check
-        cfg = self.config
         packed = bert_pack(host(input_ids), host(attention_mask), host(token_type_ids),
                            roberta=self.embeddings.roberta_positions, pad_id=self.embeddings.pad_id)
         if packed is None:
@@ -874,24 +868,48 @@ class BertEncoder(nn.Module):
                 or (tts is not None and (int(tts.min()) < 0 or int(tts.max()) >= emb.token_type_embeddings.num_embeddings))):
             return None                        # the padded path raises for these, as HF does
         N, T = len(lens), ids.shape[0]
-        d, nh = cfg.hidden_size, cfg.num_attention_heads
-        hd = d // nh
         cu = torch.zeros(N + 1, dtype=torch.int64)
         cu[1:] = torch.tensor(lens, dtype=torch.int64).cumsum(0)
         tiles = torch.from_numpy(_ops.bidir_attn_tile_list(lens, lens)).reshape(-1)
         tiles_cls = torch.from_numpy(_ops.bidir_attn_tile_list([1] * N, lens)).reshape(-1)
-        parts = [ids, pos] + ([tts] if tts is not None else []) + [cu, torch.arange(N + 1), tiles, tiles_cls]
+        tail = [cu, torch.arange(N + 1), tiles, tiles_cls]
+        if train:
+            tail += [torch.from_numpy(_ops.bidir_attn_key_tile_list(lens, lens)).reshape(-1),
+                     torch.from_numpy(_ops.bidir_attn_key_tile_list([1] * N, lens)).reshape(-1)]
+        parts = [ids, pos] + ([tts] if tts is not None else []) + tail
         dev = emb.word_embeddings.weight.device
         buf = torch.cat([p.to(torch.int32) for p in parts]).pin_memory().to(dev, non_blocking=True)   # the one upload
         views, o = [], 0
         for p in parts:
             views.append(buf[o:o + p.numel()])
             o += p.numel()
-        ids_d, pos_d = views[0], views[1]
-        tts_d = views[2] if tts is not None else None
-        cu_d, cu_cls, tiles_d, tiles_cls_d = [t for t in views[-4:]]
-        tiles_d, tiles_cls_d = tiles_d.view(-1, 2), tiles_cls_d.view(-1, 2)
-        cls_idx = cu_d[:-1]                                       # the first packed token of every sequence is its CLS token
+        tv = views[-len(tail):]
+        pk = SimpleNamespace(N=N, T=T, lens=lens, ids=views[0], pos=views[1], tts=views[2] if tts is not None else None,
+                             cu=tv[0], cu_cls=tv[1], tiles=tv[2].view(-1, 2), tiles_cls=tv[3].view(-1, 2))
+        if train:
+            pk.k_tiles, pk.k_tiles_cls = tv[4].view(-1, 2), tv[5].view(-1, 2)
+        pk.cls_idx = pk.cu[:-1]                                   # the first packed token of every sequence is its CLS token
+        return pk
+
+    def pooled_cls(self, input_ids, attention_mask, token_type_ids=None):
+        """== forward(...).last_hidden_state[:, 0] (the CLS rows the reference pools, modeling.py:231-232) for 0/1 masks whose
+        first column is set, computed on packed tokens by the hand-written forward (bert_ops.hip): no pad token is computed,
+        attention is variable-length and non-causal, LayerNorm and GELU are fused kernels, and the LAST block computes K / V for
+        every token but Q, attention, the output dense, LayerNorm and FFN for the N CLS rows only.  Returns [N, d], or None to
+        decline (the caller then runs the padded forward): grad enabled, training with dropout, f32 / CPU model, head_dim
+        outside {32, 64}, a mask that is not 0/1, a row whose first token is masked, ids out of their tables, BERT_NATIVE off.
+        Host tensors (what a tokenizer returns) are checked and packed on the host and uploaded once: no device sync."""
+        if attention_mask is None or self.native_decline_reason() is not None:
+            return None
+        pk = self._pack_upload(input_ids, attention_mask, token_type_ids)
+        if pk is None:
+            return None
+        cfg, emb = self.config, self.embeddings
+        ids_d, pos_d, tts_d, cu_d, cu_cls, tiles_d, tiles_cls_d, cls_idx = (pk.ids, pk.pos, pk.tts, pk.cu, pk.cu_cls, pk.tiles,
+                                                                            pk.tiles_cls, pk.cls_idx)
+        N, T = pk.N, pk.T
+        d, nh = cfg.hidden_size, cfg.num_attention_heads
+        hd = d // nh
         x = _ops.bert_embed_ln(ids_d, pos_d, tts_d, emb.word_embeddings.weight, emb.token_type_embeddings.weight,
                                emb.position_embeddings.weight, emb.LayerNorm.weight, emb.LayerNorm.bias, emb.LayerNorm.eps)
         scale = 1.0 / math.sqrt(hd)
@@ -922,9 +940,98 @@ class BertEncoder(nn.Module):
                                    out.LayerNorm.eps)
         return x
 
+    def native_train_decline_reason(self) -> Optional[str]:
+        """Why the packed HIP training step (`pooled_cls_train`) declines this model as it stands, or None if it takes it (the
+        mask and the ids are checked separately).  Unlike `native_decline_reason` it wants grad enabled and takes dropout."""
+        cfg, w = self.config, self.embeddings.word_embeddings.weight
+        d, nh = cfg.hidden_size, cfg.num_attention_heads
+        if not BERT_NATIVE_TRAIN:
+            return "BERT_NATIVE_TRAIN is off"
+        if not torch.is_grad_enabled():
+            return "grad disabled"
+        if not _on_hip_device(w):
+            return "not on a HIP device"
+        if w.dtype not in (torch.bfloat16, torch.float16):
+            return "storage dtype"
+        if d % nh or d // nh not in _ops.BERT_HEAD_DIMS or d % 8 or d > 4096 or cfg.intermediate_size % 8:
+            return "shape"
+        if getattr(cfg, "hidden_act", "gelu") != "gelu":
+            return "activation"
+        if self.gradient_checkpointing:
+            return "gradient checkpointing"    # the padded path keeps that feature
+        return None
+
+    def pooled_cls_train(self, input_ids, attention_mask, token_type_ids=None):
+        """`pooled_cls` with a grad graph: == forward(...).last_hidden_state[:, 0] on packed tokens, every non-GEMM op a HIP
+        kernel with a HIP backward (bert_ops.hip: attention, add + LayerNorm, embedding + LayerNorm, GELU), GEMMs F.linear under
+        autograd.  The last block computes K / V for every token and everything else for the N CLS rows, so in backward only its
+        K / V carry gradient to the non-CLS tokens.  In train mode the attention-probability dropout runs inside the attention
+        kernels (seed: one int64 per call from torch's CPU default generator, kept as `last_dropout_seed`; block i uses
+        `ops.bert_layer_seed(seed, i)`) and the hidden dropout sites go through `_hidden_dropout`.  Returns [N, d] or None to
+        decline (`native_train_decline_reason`, a mask / id condition of `pooled_cls`, or a mask that is not right-padded)."""
+        if attention_mask is None or self.native_train_decline_reason() is not None:
+            return None
+        m = attention_mask.cpu()
+        if m.dim() == 2 and m.shape[1] > 1 and bool((m[:, 1:] > m[:, :-1]).any()):
+            return None                        # a hole in the mask: training takes right-padded batches (what the collators build)
+        pk = self._pack_upload(input_ids, m, token_type_ids, train=True)
+        if pk is None:
+            return None
+        cfg, emb = self.config, self.embeddings
+        N, T = pk.N, pk.T
+        d, nh = cfg.hidden_size, cfg.num_attention_heads
+        scale = 1.0 / math.sqrt(d // nh)
+        layers = self.encoder.layer
+        p_attn = [layer.attention.self.dropout.p if self.training else 0.0 for layer in layers]
+        seed = 0
+        if any(p > 0 for p in p_attn):
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())     # CPU generator: no device sync
+        self.last_dropout_seed = seed if any(p > 0 for p in p_attn) else None     # None: this call ran without attention dropout
+
+        def drop(t, mod):
+            return _hidden_dropout(t, mod.p) if self.training and mod.p > 0 else t
+        x = _ops.bert_embed_ln_train(pk.ids, pk.pos, pk.tts, emb.word_embeddings.weight, emb.token_type_embeddings.weight,
+                                     emb.position_embeddings.weight, emb.LayerNorm.weight, emb.LayerNorm.bias, emb.LayerNorm.eps,
+                                     emb.word_embeddings.padding_idx)
+        x = drop(x, emb.dropout)
+        if len(layers) == 0:
+            return x.index_select(0, pk.cls_idx)
+        for i, layer in enumerate(layers):
+            att, so = layer.attention.self, layer.attention.output
+            lseed = _ops.bert_layer_seed(seed, i)
+            if i < len(layers) - 1:
+                # q|k|v as ONE GEMM on the concatenated weights, built per call (autograd splits the gradient back)
+                qkv = F.linear(x, torch.cat([att.query.weight, att.key.weight, att.value.weight]),
+                               torch.cat([att.query.bias, att.key.bias, att.value.bias]))
+                o = _ops.bidir_attn(qkv, None, nh, pk.cu, pk.cu, pk.tiles, pk.k_tiles, scale, p_attn[i], lseed)
+                res = x
+            else:
+                kv = F.linear(x, torch.cat([att.key.weight, att.value.weight]), torch.cat([att.key.bias, att.value.bias]))
+                res = x.index_select(0, pk.cls_idx)
+                q = F.linear(res, att.query.weight, att.query.bias)
+                o = _ops.bidir_attn(q, kv, nh, pk.cu_cls, pk.cu, pk.tiles_cls, pk.k_tiles_cls, scale, p_attn[i], lseed)
+            x = _ops.add_layernorm_train(res, drop(F.linear(o, so.dense.weight, so.dense.bias), so.dropout), so.LayerNorm.weight,
+                                         so.LayerNorm.bias, so.LayerNorm.eps)
+            h = _ops.gelu(F.linear(x, layer.intermediate.dense.weight, layer.intermediate.dense.bias))
+            out = layer.output
+            x = _ops.add_layernorm_train(x, drop(F.linear(h, out.dense.weight, out.dense.bias), out.dropout),
+                                         out.LayerNorm.weight, out.LayerNorm.bias, out.LayerNorm.eps)
+        return x
+
 
 BERT_NATIVE = True       # BertEncoder.pooled_cls runs the packed hand-written forward; False: it declines and the padded PyTorch
 #                          path runs (the A/B arm of tools/bert_encode_bench.py)
+
+
+BERT_NATIVE_TRAIN = True  # BertEncoder.pooled_cls_train runs the packed hand-written training step; False: it declines and the
+#                           padded PyTorch path runs, exactly as before (the A/B arm of tools/bert_train_bench.py)
+
+
+def _hidden_dropout(x, p):
+    """The hidden-state dropout of `pooled_cls_train` (embedding output and the two `dropout(dense(..))` sites of a block):
+    elementwise and cheap next to the GEMMs, so it stays the stock op and keeps torch's RNG semantics.  One module-level
+    function, so that a test can wrap it and record the masks."""
+    return F.dropout(x, p, True)
 
 
 def _on_hip_device(t) -> bool:

@@ -131,6 +131,11 @@ class ModelForTraining(nn.Module):
             # fell back: the packed path's check already synchronised on this mask once; its verdict spares the padded path's own
             outputs = self.model(**inputs, return_dict=True, right_padded=self.model.last_right_padded[0])
         else:
+            if self.pooling_mode == "cls" and torch.is_grad_enabled() and hasattr(self.model, "pooled_cls_train"):
+                # BERT / XLM-R: the packed hand-written training step on the real tokens only (None: it declined this batch or model)
+                pooled = self.model.pooled_cls_train(inputs["input_ids"], inputs["attention_mask"], inputs.get("token_type_ids"))
+                if pooled is not None:
+                    return ops.pool_normalize(pooled[:, None, :], None, "cls", self.normalize_embeddings)
             outputs = self.model(**inputs, return_dict=True)
         last_hidden_state = outputs.last_hidden_state
         attention_mask = inputs["attention_mask"]

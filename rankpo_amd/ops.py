@@ -1194,6 +1194,266 @@ def bert_embed_ln(ids, pos, token_types, word, type_emb, pos_emb, weight, bias, 
 
 
 # ------------------------------------------------------------------------------------------------
+# (10) packed TRAINING step of the BERT / XLM-R block (BertEncoder.pooled_cls_train): autograd over bert_ops.hip.  GEMMs stay
+# F.linear under torch's autograd.
+# ------------------------------------------------------------------------------------------------
+def bidir_attn_key_tile_list(lens_q, lens_k, k_block: int = BIDIR_ATTN_Q_BLOCK):
+    """The work list of the dK/dV kernel of `bidir_attn_bwd` as a host numpy int32 [n, 2] = (sequence id, first key row): one
+    entry per (sequence, block of k_block keys), sequences with the most queries first (their entries run longest)."""
+    return bidir_attn_tile_list(lens_k, lens_q, k_block)
+
+
+def bert_layer_seed(seed: int, layer: int) -> int:
+    """The attention-dropout seed of block `layer` for a call's `seed`: seed + layer * 0x9E3779B97F4A7C15 mod 2^64 (an odd
+    multiplier: distinct layers get distinct seeds)."""
+    return (int(seed) + int(layer) * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+
+
+def _heads_ok(who, hd, *ts):
+    for t in ts:
+        if t.stride(2) != 1 or t.stride(1) != hd:
+            raise ValueError(f"{who}: heads must be contiguous inside a token row")
+
+
+def bidir_attn_train_fwd(q, k, v, cu_q, cu_k, tiles, scale, p_drop: float = 0.0, seed: int = 0):
+    """`bidir_attn_fwd` with attention-probability dropout (p_drop = 0: none); always returns (out, lse): lse and the row sums
+    come from the undropped probabilities, out = (P * keep / (1 - p_drop)) V with keep from `bidir_attn_dropout_mask`'s function."""
+    lib = _lib.load()
+    Tq, nh, hd = q.shape
+    _heads_ok("bidir_attn_train_fwd", hd, q, k, v)
+    out = torch.empty((Tq, nh * hd), dtype=q.dtype, device=q.device)
+    lse = torch.empty((nh, Tq), dtype=torch.float32, device=q.device)
+    with torch.cuda.device(q.device):
+        check(lib.rpo_bidir_attn_train_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(0), k.stride(0), v.stride(0),
+                                           cu_q.data_ptr(), cu_k.data_ptr(), tiles.data_ptr(), tiles.shape[0], tiles.shape[1],
+                                           BIDIR_ATTN_Q_BLOCK, Tq, nh, k.shape[1], hd, _dt(q), float(scale), float(p_drop),
+                                           int(seed), out.data_ptr(), nh * hd, lse.data_ptr(), _stream(q)),
+              "rpo_bidir_attn_train_fwd")
+    return out, lse
+
+
+def bidir_attn_bwd(q, k, v, out, dout, lse, cu_q, cu_k, q_tiles, k_tiles, scale, dq, dk, dv, p_drop: float = 0.0, seed: int = 0):
+    """Backward of `bidir_attn_fwd` / `bidir_attn_train_fwd` into dq / dk / dv ([T, nh, hd] views, token stride free: column
+    blocks of one fused gradient buffer).  k_tiles from `bidir_attn_key_tile_list`.  Returns (dq, dk, dv)."""
+    lib = _lib.load()
+    Tq, nh, hd = q.shape
+    _heads_ok("bidir_attn_bwd", hd, q, k, v, dq, dk, dv)
+    if out.stride(1) != 1 or dout.stride(1) != 1:
+        raise ValueError("bidir_attn_bwd: out / dout rows must be contiguous")
+    with torch.cuda.device(q.device):
+        check(lib.rpo_bidir_attn_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(0), k.stride(0), v.stride(0),
+                                     out.data_ptr(), out.stride(0), dout.data_ptr(), dout.stride(0), lse.data_ptr(),
+                                     cu_q.data_ptr(), cu_k.data_ptr(), q_tiles.data_ptr(), q_tiles.shape[0], k_tiles.data_ptr(),
+                                     k_tiles.shape[0], q_tiles.shape[1], BIDIR_ATTN_Q_BLOCK, Tq, nh, k.shape[1], hd, _dt(q),
+                                     float(scale), float(p_drop), int(seed), dq.data_ptr(), dq.stride(0), dk.data_ptr(),
+                                     dk.stride(0), dv.data_ptr(), dv.stride(0), _stream(q)), "rpo_bidir_attn_bwd")
+    return dq, dk, dv
+
+
+def bidir_attn_dropout_mask(q_row0: int, k_row0: int, len_q: int, len_k: int, num_heads: int, p_drop: float, seed: int, device,
+                            head0: int = 0):
+    """The keep mask (uint8 [num_heads, len_q, len_k], 1 = kept) the attention kernels use for packed query rows q_row0.. and
+    packed key rows k_row0.. of one sequence.  Tests and diagnostics: the product never calls it."""
+    lib = _lib.load()
+    mask = torch.empty((num_heads, len_q, len_k), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        check(lib.rpo_bidir_attn_dropout_mask(q_row0, k_row0, len_q, len_k, head0, num_heads, float(p_drop), int(seed),
+                                              mask.data_ptr(), torch.cuda.current_stream(device).cuda_stream),
+              "rpo_bidir_attn_dropout_mask")
+    return mask
+
+
+class _BidirAttn(torch.autograd.Function):
+    """Packed bidirectional attention over ONE fused projection output.  `kv` None: a = q|k|v [T, 3 d] (self-attention of every
+    token); else a = q [Nq, d] and kv = k|v [T, 2 d] (the last block: one CLS query per sequence).  The backward writes the
+    gradient of each fused buffer in place of its column blocks: no concatenation."""
+
+    @staticmethod
+    def forward(ctx, a, kv, nh, cu_q, cu_k, q_tiles, k_tiles, scale, p_drop, seed):
+        d = a.shape[1] if kv is not None else a.shape[1] // 3
+        hd = d // nh
+        ctx.dims = (nh, hd, d, float(scale), float(p_drop), int(seed))
+        q, k, v = _BidirAttn._views(a, kv, nh, hd, d)
+        out, lse = bidir_attn_train_fwd(q, k, v, cu_q, cu_k, q_tiles, scale, p_drop, seed)
+        ctx.save_for_backward(a, kv, out, lse, cu_q, cu_k, q_tiles, k_tiles)
+        return out
+
+    @staticmethod
+    def _views(a, kv, nh, hd, d):
+        if kv is None:
+            return tuple(a[:, j * d:(j + 1) * d].view(-1, nh, hd) for j in range(3))
+        return a.view(-1, nh, hd), kv[:, :d].view(-1, nh, hd), kv[:, d:].view(-1, nh, hd)
+
+    @staticmethod
+    def backward(ctx, go):
+        a, kv, out, lse, cu_q, cu_k, q_tiles, k_tiles = ctx.saved_tensors
+        nh, hd, d, scale, p_drop, seed = ctx.dims
+        go = go if go.stride(1) == 1 and go.stride(0) % 8 == 0 and go.data_ptr() % 16 == 0 else go.contiguous()
+        da = torch.empty_like(a)
+        dkv = None if kv is None else torch.empty_like(kv)
+        q, k, v = _BidirAttn._views(a, kv, nh, hd, d)
+        dq, dk, dv = _BidirAttn._views(da, dkv, nh, hd, d)
+        bidir_attn_bwd(q, k, v, out, go, lse, cu_q, cu_k, q_tiles, k_tiles, scale, dq, dk, dv, p_drop, seed)
+        return (da, dkv) + (None,) * 8
+
+
+def bidir_attn(a, kv, num_heads, cu_q, cu_k, q_tiles, k_tiles, scale, p_drop: float = 0.0, seed: int = 0):
+    """Differentiable packed bidirectional attention (see `_BidirAttn`) -> [Tq, d]."""
+    if not a.is_contiguous() or (kv is not None and not kv.is_contiguous()):
+        raise ValueError("bidir_attn: the fused projection outputs must be contiguous")
+    return _BidirAttn.apply(a, kv, num_heads, cu_q, cu_k, q_tiles, k_tiles, scale, p_drop, seed)
+
+
+def layernorm_bwd(s, weight, dy, eps):
+    """(ds, dgamma, dbeta) of y = LayerNorm(s) * weight + bias from the stored rounded sum s [rows, d]; dgamma / dbeta f32."""
+    lib = _lib.load()
+    rows, d = s.shape
+    dy = dy if dy.stride(1) == 1 and dy.stride(0) % 8 == 0 and dy.data_ptr() % 16 == 0 else dy.contiguous()
+    ds = torch.empty((rows, d), dtype=s.dtype, device=s.device)
+    if rows == 0:
+        z = torch.zeros((d,), dtype=torch.float32, device=s.device)
+        return ds, z, z.clone()
+    nb = lib.rpo_layernorm_bwd_blocks(rows)
+    part = torch.empty((2, nb, d), dtype=torch.float32, device=s.device)
+    with torch.cuda.device(s.device):
+        check(lib.rpo_layernorm_bwd(s.data_ptr(), s.stride(0), weight.data_ptr(), dy.data_ptr(), dy.stride(0), float(eps),
+                                    ds.data_ptr(), d, part[0].data_ptr(), part[1].data_ptr(), rows, d, _dt(s), _stream(s)),
+              "rpo_layernorm_bwd")
+    sums = part.sum(1)
+    return ds, sums[0], sums[1]
+
+
+class _AddLayerNorm(torch.autograd.Function):
+    """y = LayerNorm(a + b) * weight + bias (b may be None) with the backward kernel: ds is the gradient of both addends."""
+
+    @staticmethod
+    def forward(ctx, a, b, weight, bias, eps):
+        lib = _lib.load()
+        rows, d = a.shape
+        for t in (a, b):
+            if t is not None and t.stride(1) != 1:
+                raise ValueError("add_layernorm_train: rows must be contiguous")
+        y = torch.empty((rows, d), dtype=a.dtype, device=a.device)
+        s = torch.empty((rows, d), dtype=a.dtype, device=a.device)
+        with torch.cuda.device(a.device):
+            check(lib.rpo_add_layernorm_train_fwd(a.data_ptr(), a.stride(0), _p(b), b.stride(0) if b is not None else 0,
+                                                  weight.data_ptr(), bias.data_ptr(), float(eps), y.data_ptr(), d, s.data_ptr(), d,
+                                                  rows, d, _dt(a), _stream(a)), "rpo_add_layernorm_train_fwd")
+        ctx.save_for_backward(s, weight)
+        ctx.eps, ctx.has_b = float(eps), b is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        s, weight = ctx.saved_tensors
+        ds, dg, db = layernorm_bwd(s, weight, dy, ctx.eps)
+        return ds, (ds if ctx.has_b else None), dg.to(weight.dtype), db.to(weight.dtype), None
+
+
+def add_layernorm_train(a, b, weight, bias, eps):
+    """Differentiable `add_layernorm` -> a new contiguous [rows, d]."""
+    return _AddLayerNorm.apply(a, b, weight, bias, eps)
+
+
+class _BertEmbedLayerNorm(torch.autograd.Function):
+    """`bert_embed_ln` with a backward: the LayerNorm backward kernel, then ds scattered into the three tables."""
+
+    @staticmethod
+    def forward(ctx, ids, pos, token_types, word, type_emb, pos_emb, weight, bias, eps, padding_idx):
+        lib = _lib.load()
+        T, d = ids.shape[0], word.shape[1]
+        for t in (word, type_emb, pos_emb):
+            if not t.is_contiguous():
+                raise ValueError("bert_embed_ln_train: embedding tables must be contiguous")
+        y = torch.empty((T, d), dtype=word.dtype, device=word.device)
+        s = torch.empty((T, d), dtype=word.dtype, device=word.device)
+        with torch.cuda.device(word.device):
+            check(lib.rpo_bert_embed_ln_train_fwd(ids.data_ptr(), _p(token_types), pos.data_ptr(), T, word.data_ptr(),
+                                                  word.shape[0], type_emb.data_ptr(), type_emb.shape[0], pos_emb.data_ptr(),
+                                                  pos_emb.shape[0], weight.data_ptr(), bias.data_ptr(), float(eps), y.data_ptr(),
+                                                  d, s.data_ptr(), d, d, _dt(word), _stream(word)), "rpo_bert_embed_ln_train_fwd")
+        ctx.save_for_backward(s, weight, ids, pos, token_types)
+        ctx.eps, ctx.padding_idx = float(eps), padding_idx
+        ctx.tables = (word.shape, type_emb.shape, pos_emb.shape)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        s, weight, ids, pos, token_types = ctx.saved_tensors
+        ds, dg, db = layernorm_bwd(s, weight, dy, ctx.eps)
+        # Embedding gradient = plumbing: stock index_add_ of ds into f32 tables.  It is atomic-based (the order of the adds into one
+        # row is not fixed), like the padded path's own embedding backward; every other gradient of the native step is deterministic.
+        # Cost: one dense f32 [rows, d] table per embedding and call plus its storage-dtype copy (the word table of XLM-R /
+        # bge-m3, 250002 x 1024: 1 GB f32 + 0.5 GB): twice the bytes of the padded path's storage-dtype dense gradient, bought
+        # for sums of many token rows that do not round after every add.
+        ds32 = ds.float()
+
+        def scatter(shape, idx):
+            return torch.zeros(shape, dtype=torch.float32, device=ds.device).index_add_(0, idx.long(), ds32)
+        dword = dpos = dtype_emb = None
+        if ctx.needs_input_grad[3]:
+            dword = scatter(ctx.tables[0], ids)
+            if ctx.padding_idx is not None:
+                dword[ctx.padding_idx].zero_()             # nn.Embedding(padding_idx=..) keeps that row's gradient at zero
+            dword = dword.to(s.dtype)
+        if ctx.needs_input_grad[4]:
+            if token_types is None:                        # type 0 for every token
+                dtype_emb = torch.zeros(ctx.tables[1], dtype=torch.float32, device=ds.device)
+                dtype_emb[0] = ds32.sum(0)
+            else:
+                dtype_emb = scatter(ctx.tables[1], token_types)
+            dtype_emb = dtype_emb.to(s.dtype)
+        if ctx.needs_input_grad[5]:
+            dpos = scatter(ctx.tables[2], pos).to(s.dtype)
+        return None, None, None, dword, dtype_emb, dpos, dg.to(weight.dtype), db.to(weight.dtype), None, None
+
+
+def bert_embed_ln_train(ids, pos, token_types, word, type_emb, pos_emb, weight, bias, eps, padding_idx=None):
+    """Differentiable `bert_embed_ln` (gradients to the three tables and the LayerNorm parameters)."""
+    return _BertEmbedLayerNorm.apply(ids, pos, token_types, word, type_emb, pos_emb, weight, bias, eps, padding_idx)
+
+
+def gelu_out(u):
+    """Exact erf GELU out of place over a 2-D row-strided u -> a new contiguous tensor (u survives for the backward)."""
+    lib = _lib.load()
+    if u.dim() != 2 or u.stride(1) != 1:
+        raise ValueError("gelu_out: 2-D with contiguous rows")
+    h = torch.empty(u.shape, dtype=u.dtype, device=u.device)
+    with torch.cuda.device(u.device):
+        check(lib.rpo_gelu_out_fwd(u.data_ptr(), u.stride(0), h.data_ptr(), h.stride(0), u.shape[0], u.shape[1], _dt(u),
+                                   _stream(u)), "rpo_gelu_out_fwd")
+    return h
+
+
+def gelu_bwd(u, dh):
+    """du = dh * (Phi(u) + u phi(u)) -> a new contiguous tensor."""
+    lib = _lib.load()
+    dh = dh if dh.stride(1) == 1 and dh.stride(0) % 8 == 0 and dh.data_ptr() % 16 == 0 else dh.contiguous()
+    du = torch.empty(u.shape, dtype=u.dtype, device=u.device)
+    with torch.cuda.device(u.device):
+        check(lib.rpo_gelu_bwd(u.data_ptr(), u.stride(0), dh.data_ptr(), dh.stride(0), du.data_ptr(), du.stride(0), u.shape[0],
+                               u.shape[1], _dt(u), _stream(u)), "rpo_gelu_bwd")
+    return du
+
+
+class _Gelu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u):
+        ctx.save_for_backward(u)
+        return gelu_out(u)
+
+    @staticmethod
+    def backward(ctx, dh):
+        (u,) = ctx.saved_tensors
+        return gelu_bwd(u, dh)
+
+
+def gelu(u):
+    """Differentiable exact erf GELU (HIP forward and backward)."""
+    return _Gelu.apply(u)
+
+
+# ------------------------------------------------------------------------------------------------
 # (8) exact top-k over score chunks (retrieval, "next" row f3)
 # ------------------------------------------------------------------------------------------------
 TOPK_MAX_K = 1024
