@@ -183,7 +183,7 @@ int rpo_rankpo_bwd(const void* q, const void* p, const float* dscores, const flo
  * torch.optim.AdamW semantics on n elements (n % 4 == 0, 16-byte aligned buffers):
  *   g = grad * (grad_scale ? grad_scale[0] : 1);  w *= 1 - lr*wd;  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2
  *   w -= (lr / bias_corr1) * m / (sqrt(v) / sqrt(bias_corr2) + eps)
- * dtype = storage type of param and grad.  bf16 params need an f32 `master` copy (updated, then rounded into
+ * dtype = storage type of param and grad (RPO_DT_F32 / RPO_DT_BF16; fp16: rpo_adamw_step_scaled below).  bf16 params need an f32 `master` copy (updated, then rounded into
  * param); for f32 params master may be NULL.  grad_scale: device f32 scalar or NULL (clip / 1/GAS factor).
  * rpo_sumsq_partial: partial_out[b] = sum of squares of block b's share of x (for the global grad norm).
  * --------------------------------------------------------------------------------------------- */
@@ -191,6 +191,55 @@ int rpo_adamw_step(void* param, float* master, const void* grad, float* exp_avg,
                    int dtype, float lr, float beta1, float beta2, float eps, float weight_decay,
                    float bias_corr1, float bias_corr2, const float* grad_scale, rpo_stream_t stream);
 int rpo_sumsq_partial(const void* x, int64_t n, int dtype, float* partial_out, int nblocks, rpo_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * (4b) fp16 training: dynamic loss scaling on the device + the AdamW step that obeys it.  Stands where the reference's
+ * fp16 BGE run has DeepSpeed's DynamicLossScaler (configs/ds_zero1_config_bge.json:2-11: loss_scale 0, initial_scale_power 16,
+ * loss_scale_window 1000, hysteresis 2, consecutive_hysteresis false, min_loss_scale 1).  No value visits the host.
+ *
+ * rpo_sumsq_partial takes RPO_DT_F16 for this (it answered RPO_ERR_INVALID_ARG before; nothing else about it changed).  The sum
+ * of its partials is the overflow check: squares of finite fp16 values summed in f32 cannot overflow for any buffer that fits
+ * in memory, so the sum is non-finite exactly when some gradient element is inf or NaN.
+ *
+ * State block: RPO_LS_WORDS 32-bit words in device memory, 16-byte aligned, indexed by rpo_ls_word.  SCALE, MULT and NORM are
+ * f32, the others int32.  Initial state: SCALE = 2^initial_scale_power (or the static scale), CUR_HYSTERESIS = hysteresis,
+ * everything else 0.  Words 9..15 are reserved (zero).
+ *
+ * rpo_loss_scale_update (one launch, one working thread): sumsq = device scalar, the sum of squares of the SCALED accumulated
+ * gradient (after the rank all-reduce when the optimizer state is partitioned); pre_scale = 1 / GAS / world; max_grad_norm <= 0:
+ * no clipping.  With s = SCALE on entry:
+ *   SKIP = sumsq is inf or NaN;  NORM = sqrt(sumsq) pre_scale / s;
+ *   MULT = pre_scale / s * min(1, max_grad_norm / (NORM + 1e-6))   (0 when SKIP; NORM and MULT are computed in f64, rounded once)
+ *   SKIP:  SKIPPED_STEPS += 1; and when dynamic:  FLOOR_HITS += 1 if s <= min_scale (DeepSpeed raises there; here it is counted);
+ *          if hysteresis == 1 or CUR_HYSTERESIS == 1: SCALE = max(s / 2, min_scale)   else: CUR_HYSTERESIS -= 1;   GOOD_STEPS = 0
+ *   else:  APPLIED_STEPS += 1; and when dynamic:  GOOD_STEPS += 1;  if consecutive_hysteresis: CUR_HYSTERESIS = hysteresis;
+ *          if GOOD_STEPS % window == 0: { if !consecutive_hysteresis: CUR_HYSTERESIS = hysteresis;  SCALE = 2 s }
+ * dynamic == 0 is a static scale: SCALE, GOOD_STEPS and CUR_HYSTERESIS stay, an overflow still skips the step.
+ * window >= 1, hysteresis >= 1, pre_scale > 0, min_scale > 0 (RPO_ERR_INVALID_ARG otherwise).
+ *
+ * rpo_adamw_step_scaled: rpo_adamw_step for RPO_DT_F16 parameters and gradients with an f32 master (required), m and v --
+ * 28 B/element as bf16 -- driven by the state block as rpo_loss_scale_update left it: SKIP != 0 writes NOTHING; otherwise
+ * g = grad * MULT, bias_corr1 = 1 - beta1^APPLIED_STEPS and bias_corr2 likewise (f64 powers of the f32 betas as passed, rounded to f32 once), and the
+ * stored parameter is the round-to-nearest-even fp16 of the new master.  Other dtypes: RPO_ERR_UNSUPPORTED (rpo_adamw_step
+ * serves them).
+ * --------------------------------------------------------------------------------------------- */
+typedef enum {
+    RPO_LS_SCALE = 0,            /* f32  loss scale the NEXT backward runs under */
+    RPO_LS_MULT = 1,             /* f32  factor on the stored gradient in this step's AdamW */
+    RPO_LS_NORM = 2,             /* f32  unscaled global gradient norm of this step (non-finite when skipped) */
+    RPO_LS_SKIP = 3,             /* i32  1: this step's gradient overflowed, AdamW writes nothing */
+    RPO_LS_GOOD_STEPS = 4,       /* i32  steps without overflow since the last one */
+    RPO_LS_CUR_HYSTERESIS = 5,   /* i32 */
+    RPO_LS_APPLIED_STEPS = 6,    /* i32  steps AdamW applied: the bias-correction step count */
+    RPO_LS_SKIPPED_STEPS = 7,    /* i32 */
+    RPO_LS_FLOOR_HITS = 8,       /* i32  overflows met at SCALE <= min_scale */
+    RPO_LS_WORDS = 16
+} rpo_ls_word;
+int rpo_loss_scale_update(const float* sumsq, void* ls_state, float pre_scale, float max_grad_norm, int dynamic, int window,
+                          int hysteresis, int consecutive_hysteresis, float min_scale, rpo_stream_t stream);
+int rpo_adamw_step_scaled(void* param, float* master, const void* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                          int dtype, float lr, float beta1, float beta2, float eps, float weight_decay, const void* ls_state,
+                          rpo_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * (5) fused elementwise pieces of the Llama block used by rankpo_amd/encoder.py (the encoder itself stays under

@@ -10,8 +10,10 @@ _lib.load()
 from .modeling import ModelForInference, ModelForTraining, ModelOutput  # noqa: E402
 from .rankpo_trainer import RankPOTrainer  # noqa: E402
 from .data_utils import ContrastiveDataCollatorWithPadding, RankPODataCollatorWithPadding  # noqa: E402
+from .train_step import FlatAdamW, LossScaleConfig, TrainStep  # noqa: E402
 from . import ops  # noqa: E402
 
 __all__ = ["ModelForTraining", "ModelForInference", "ModelOutput", "RankPOTrainer",
-           "ContrastiveDataCollatorWithPadding", "RankPODataCollatorWithPadding", "ops"]
+           "ContrastiveDataCollatorWithPadding", "RankPODataCollatorWithPadding", "TrainStep", "FlatAdamW",
+           "LossScaleConfig", "ops"]
 __version__ = "0.1.0"

@@ -14,6 +14,10 @@ LIB_PATH = os.path.join(_HERE, "csrc", "librankpo_hip.so")
 RPO_OK = 0
 RPO_DT_F32, RPO_DT_BF16, RPO_DT_F16 = 0, 1, 2
 RPO_POOL_LAST, RPO_POOL_CLS = 0, 1
+# rpo_ls_word: the loss-scale state block (f32: scale, mult, norm; int32: the rest)
+(RPO_LS_SCALE, RPO_LS_MULT, RPO_LS_NORM, RPO_LS_SKIP, RPO_LS_GOOD_STEPS, RPO_LS_CUR_HYSTERESIS, RPO_LS_APPLIED_STEPS,
+ RPO_LS_SKIPPED_STEPS, RPO_LS_FLOOR_HITS) = range(9)
+RPO_LS_WORDS = 16
 RPO_TARGET_INBATCH, RPO_TARGET_FIRST = 0, 1
 RPO_LOSS_SIGMOID, RPO_LOSS_HINGE = 0, 1
 RPO_BUILD_ONEWAVE64 = 1
@@ -57,6 +61,8 @@ SIGNATURES = {
     "rpo_rankpo_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp]),
     "rpo_adamw_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _vp]),
     "rpo_sumsq_partial": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp]),
+    "rpo_loss_scale_update": (C.c_int, [_vp, _vp, _f32, _f32, _i32, _i32, _i32, _i32, _f32, _vp]),
+    "rpo_adamw_step_scaled": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _vp, _vp]),
     "rpo_swiglu_fwd": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp]),
     "rpo_topk_merge": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _i32, _vp]),
     "rpo_topk_merge_split": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
