@@ -528,6 +528,28 @@ int rpo_sim_scores_f32(const void* q, const void* p, int64_t Q, int64_t P, int64
 int rpo_topk_merge_candidates(const float* cand_val, const int64_t* cand_idx, int32_t* cand_cnt, int64_t rows, int cap, int k,
                               float* best_val, int64_t* best_idx, int32_t* overflow, rpo_stream_t stream);
 
+/* The search of an F32 index whose values are exact in NEITHER 16-bit type (an f32 encoder's output, f32-normalised embeddings), on the
+ * same 16-bit frame: every finite f32 x is h + m + l with h = bf16(x), m = bf16(x - h), l = bf16(x - h - m) as long as the three
+ * planes are normal or zero.  The scoring frame walks the plane pairs (q, corpus) = lh, mm, hl, mh, hm, hh -- smallest terms first --
+ * into one f32 accumulator: exact products, f32 sums in this frame's order, 6 K-walks against the f32 MFMA's 16; the pairs ml, lm,
+ * ll it leaves out are below (2^-23 + 2^-32) |q_i c_i| per element, the size of the rounding of an f32 multiply.
+ * rpo_split_bf16x3: planes bf16 [rows, 3 d] (row stride ldp elements), h | m | l per row, of x f32 [rows, d] (row stride ldx);
+ *   d % 64 == 0, ldx % 4 == 0, ldp % 8 == 0, 16-byte aligned.  *inexact (device int32) is set to 1 -- never cleared -- when an
+ *   element is not finite, its planes do not add up to it in f32 ((float)h + (float)m + (float)l != x) or a plane is a bf16
+ *   subnormal: the caller then keeps the f32 kernel.
+ * rpo_sim_planes_ok(Q, P, d): the shapes of rpo_sim_topk_filter_ok applied to d, with the operand limit on the planes
+ *   (rows * 3 d * 2 bytes below 4 GB).
+ * rpo_sim_scores_f32_planes / rpo_sim_topk_filter_planes: rpo_sim_scores_f32 / rpo_sim_topk_filter(round_scores = 0) with q [Q, 3 d]
+ *   and p [P, 3 d] planes (contiguous rows) in place of the bf16 operands; everything else as there. */
+int rpo_split_bf16x3(const float* x, int64_t ldx, int64_t rows, int64_t d, void* planes, int64_t ldp, int32_t* inexact,
+                     rpo_stream_t stream);
+int rpo_sim_planes_ok(int64_t Q, int64_t P, int64_t d);
+int rpo_sim_scores_f32_planes(const void* q, const void* p, int64_t Q, int64_t P, int64_t d, float* scores, int64_t ldc,
+                              rpo_stream_t stream);
+int rpo_sim_topk_filter_planes(const void* q, const void* p, int64_t Q, int64_t P, int64_t d, int64_t col0, int k,
+                               const float* best_val, const int64_t* best_idx, float* cand_val, int64_t* cand_idx,
+                               int32_t* cand_cnt, int cap, rpo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -357,6 +357,16 @@ __device__ __forceinline__ int big_unit_row(int unit, int u) {
 //          (F16 = true: the same for values exact in fp16 -- an fp16 encoder's output -- with the f16 MFMA.)
 // EPI = 4: the score matrix of the same problem as f32 (`scores` is a float*, ldc its row stride in elements), direct 16-byte
 // stores: the first chunk of such a search (small), so that every score of it comes out of ONE summation order.
+// PLANES (EPI 3 / 4, bf16 operands): the exact search of an f32 index whose values are NOT exact in 16 bits.  Both operands are
+// [rows, 3 d] bf16 PLANES h | m | l of the f32 rows (x == h + m + l exactly: rpo_split_bf16x3, topk.hip), lda = ldb = 3 d, and the
+// K loop walks the six plane pairs of kPlanePairs, smallest terms first, into the SAME accumulators: 6 d / 64 K-steps whose
+// staging offsets are (plane d + kk 64) 2 bytes instead of T 128.  Products of bf16 values are exact in f32, so the score is again
+// "exact products, f32 sums in this frame's order"; the pairs ml, lm, ll that are left out are below (2 2^-24 + 2^-32) |q_i c_i|
+// per element, what an f32 multiply rounds away anyway.  The pair and the step inside it are wave-uniform (scalar registers); the
+// loop, its counted waits and its barriers are those of the one-plane walk.
+constexpr int kPlanePairs = 6;
+constexpr unsigned kPlanesQ = 2u | (1u << 2) | (0u << 4) | (1u << 6) | (0u << 8) | (0u << 10);      // q:      l, m, h, m, h, h
+constexpr unsigned kPlanesP = 0u | (1u << 2) | (2u << 4) | (0u << 6) | (1u << 8) | (0u << 10);      // corpus: h, m, l, h, m, h
 struct SimFilter {
     const float* best_val;        // [Q, k] winners so far, best first: row r's threshold is (best_val, best_idx)[r k + k - 1]
     const long long* best_idx;
@@ -377,11 +387,12 @@ __device__ __forceinline__ float4_t big_mma(const short8_t a, const short8_t b, 
         return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
-template <int EPI, bool F16 = false>
+template <int EPI, bool F16 = false, bool PLANES = false>
 __global__ __launch_bounds__(kBigThreads, 2) void sim_tile256_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ p, int64_t Q, int64_t P, int64_t d, int64_t lda, int64_t ldb,
     int64_t ldc, float temperature, int scale, int do_stats_arg, bf16_t* __restrict__ scores, float2* __restrict__ partial,
     int nPt, int nQt, int stagger, int dbg, const SimFilter flt) {
+    static_assert(!PLANES || ((EPI == 3 || EPI == 4) && !F16), "planes: the unrounded f32 epilogues, bf16 operands");
     const int do_stats = EPI == 0 ? do_stats_arg : 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef short8_t Frag;
@@ -429,18 +440,32 @@ __global__ __launch_bounds__(kBigThreads, 2) void sim_tile256_kernel(
             }
     };
     set_src(p0, q0);
+    // K-step T of a unit starts T * 128 bytes into the row; PLANES: at the step's plane of that operand (koff_p / koff_q, below)
 #define RPO_BIG_STAGE(U, T, BUF)                                                                                   \
     do {                                                                                                           \
         _Pragma("unroll") for (int j_ = 0; j_ < 2; ++j_) {                                                         \
             char* dst_ = smem + (BUF) * kBigBufBytes + (U) * kBigUnitBytes + (8 * j_ + wave) * 1024;               \
             const char* base_ = reinterpret_cast<const char*>(((U) == 0 || (U) == 3) ? p : q);                     \
+            const unsigned koff_ = PLANES ? (((U) == 0 || (U) == 3) ? koff_p : koff_q) : (unsigned)(T) * (KE * 2); \
             __builtin_amdgcn_global_load_lds(                                                                      \
-                (const __attribute__((address_space(1))) void*)(base_ + (soff[U][j_] + (unsigned)(T) * (KE * 2))), \
+                (const __attribute__((address_space(1))) void*)(base_ + (soff[U][j_] + koff_)),                    \
                 (__attribute__((address_space(3))) void*)dst_, 16, 0, 0);                                          \
         }                                                                                                          \
     } while (0)
 
-    const int nk = (int)(d / KE);
+    const int nkd = (int)(d / KE);                              // K-steps per plane (pair)
+    const int nk = PLANES ? kPlanePairs * nkd : nkd;
+    // PLANES: byte offsets of the K-step that is staged NEXT inside the corpus / query row, and that step as (pair, step in the pair);
+    // all wave-uniform.  plane_step(0, 0) is a tile's first K-step; the loop advances it once per K-step.
+    unsigned koff_p = 0, koff_q = 0;
+    int pl_s = 0, pl_kk = 0;
+    auto plane_step = [&](int s_, int kk_) {
+        pl_s = s_;
+        pl_kk = kk_;
+        koff_p = (unsigned)(((kPlanesP >> (2 * s_)) & 3u) * (unsigned)d + (unsigned)kk_ * KE) * 2u;
+        koff_q = (unsigned)(((kPlanesQ >> (2 * s_)) & 3u) * (unsigned)d + (unsigned)kk_ * KE) * 2u;
+    };
+    if constexpr (PLANES) plane_step(0, 0);
     // per-lane read offsets inside a unit (row part); the chunk part depends on the k-step
     const int a_off = (wp * 64 + frow) * kTileRowBytes;         // + m*16 rows, units 0 / 3
     const int b_off = (wq * 32 + frow) * kTileRowBytes;         // + n*16 rows, units 1 / 2
@@ -496,6 +521,10 @@ __global__ __launch_bounds__(kBigThreads, 2) void sim_tile256_kernel(
         const int cur = t & 1, nxt = cur ^ 1;
         const bool more = t + 1 < nk;
         const char* base = smem + cur * kBigBufBytes;
+        if constexpr (PLANES) {                                 // K-step t + 1 (behind the last: pair 6, whose table entries are 0; not staged)
+            if (pl_kk + 1 < nkd) plane_step(pl_s, pl_kk + 1);
+            else plane_step(pl_s + 1, 0);
+        }
         // ---------------- phase 0
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
@@ -588,6 +617,7 @@ __global__ __launch_bounds__(kBigThreads, 2) void sim_tile256_kernel(
     const int64_t p0e = p0, q0e = q0;      // this tile's origin, for the epilogue
     const int pte = pt;
     const bool have_next = vb + (int)gridDim.x < nwg;
+    if constexpr (PLANES) plane_step(0, 0);
     if (have_next) {
         tile_of(vb + (int)gridDim.x, p0, q0, pt);
         set_src(p0, q0);
@@ -1846,6 +1876,54 @@ extern "C" int rpo_sim_scores_f32(const void* q, const void* p, int64_t Q, int64
         RPO_LAUNCH((sim_tile256_kernel<4>), grid, dim3(kBigThreads), kBigLdsBytes, (hipStream_t)stream, (const bf16_t*)q,
                    (const bf16_t*)p, Q, P, d, d, d, ldc, 1.0f, 0, 0, (bf16_t*)scores, (float2*)nullptr, (int)nPt, (int)nQt,
                    /*stagger=*/1, /*dbg=*/0, SimFilter{});
+    return rpo_launch_status();
+}
+
+// ---- the same two calls on bf16 PLANES of f32 operands (sim_tile256_kernel<3 / 4, false, true>): q [Q, 3 d], p [P, 3 d] as
+// rpo_split_bf16x3 writes them.  Shapes: rpo_sim_topk_filter_ok applied to d, with the 32-bit piece offsets covering a whole
+// plane row (rows * 3 d * 2 bytes below 4 GB).
+extern "C" int rpo_sim_planes_ok(int64_t Q, int64_t P, int64_t d) {
+    if (!rpo_sim_topk_filter_ok(Q, P, d)) return 0;
+    return P * 3 * d * 2 < ((int64_t)1 << 32) && Q * 3 * d * 2 < ((int64_t)1 << 32) ? 1 : 0;
+}
+
+extern "C" int rpo_sim_topk_filter_planes(const void* q, const void* p, int64_t Q, int64_t P, int64_t d, int64_t col0, int k,
+                                          const float* best_val, const int64_t* best_idx, float* cand_val, int64_t* cand_idx,
+                                          int32_t* cand_cnt, int cap, rpo_stream_t stream) {
+    if (!q || !p || !best_val || !best_idx || !cand_val || !cand_idx || !cand_cnt || Q <= 0 || P <= 0 || d <= 0 || col0 < 0 ||
+        k <= 0 || cap <= 0)
+        return RPO_ERR_INVALID_ARG;
+    if (!rpo_aligned16(q) || !rpo_aligned16(p) || !rpo_sim_planes_ok(Q, P, d)) return RPO_ERR_UNSUPPORTED;
+    const int64_t nPt = rpo_cdiv(P, kBigTile), nQt = rpo_cdiv(Q, kBigTile);
+    if (nPt * nQt > 0x7fffffff) return RPO_ERR_UNSUPPORTED;
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)sim_tile256_kernel<3, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kBigLdsBytes);
+        attr_set = true;
+    }
+    SimFilter flt{best_val, (const long long*)best_idx, cand_val, (long long*)cand_idx, cand_cnt, col0, k, cap};
+    const dim3 grid((unsigned)std::min<int64_t>(nPt * nQt, kBigPersistBlocks));
+    RPO_LAUNCH((sim_tile256_kernel<3, false, true>), grid, dim3(kBigThreads), kBigLdsBytes, (hipStream_t)stream, (const bf16_t*)q,
+               (const bf16_t*)p, Q, P, d, 3 * d, 3 * d, P, 1.0f, 0, 0, (bf16_t*)nullptr, (float2*)nullptr, (int)nPt, (int)nQt,
+               /*stagger=*/1, /*dbg=*/0, flt);
+    return rpo_launch_status();
+}
+
+extern "C" int rpo_sim_scores_f32_planes(const void* q, const void* p, int64_t Q, int64_t P, int64_t d, float* scores, int64_t ldc,
+                                         rpo_stream_t stream) {
+    if (!q || !p || !scores || Q <= 0 || P <= 0 || d <= 0 || ldc < P) return RPO_ERR_INVALID_ARG;
+    if (!rpo_aligned16(q) || !rpo_aligned16(p) || !rpo_sim_planes_ok(Q, P, d)) return RPO_ERR_UNSUPPORTED;
+    const int64_t nPt = rpo_cdiv(P, kBigTile), nQt = rpo_cdiv(Q, kBigTile);
+    if (nPt * nQt > 0x7fffffff) return RPO_ERR_UNSUPPORTED;
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)sim_tile256_kernel<4, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kBigLdsBytes);
+        attr_set = true;
+    }
+    const dim3 grid((unsigned)std::min<int64_t>(nPt * nQt, kBigPersistBlocks));
+    RPO_LAUNCH((sim_tile256_kernel<4, false, true>), grid, dim3(kBigThreads), kBigLdsBytes, (hipStream_t)stream, (const bf16_t*)q,
+               (const bf16_t*)p, Q, P, d, 3 * d, 3 * d, ldc, 1.0f, 0, 0, (bf16_t*)scores, (float2*)nullptr, (int)nPt, (int)nQt,
+               /*stagger=*/1, /*dbg=*/0, SimFilter{});
     return rpo_launch_status();
 }
 

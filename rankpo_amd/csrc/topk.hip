@@ -8,6 +8,8 @@
 // re-selects (bitonic sort of winners + candidates, 4096 slots) whenever the list could overflow during the next segment.
 // After the first few segments the k-th winner is high and almost nothing passes the filter, so the kernel is one
 // coalesced pass over the scores.
+#include <algorithm>
+
 #include "common.hpp"
 
 namespace {
@@ -334,7 +336,65 @@ __global__ __launch_bounds__(kTopkThreads) void topk_merge_cand_kernel(const flo
     }
 }
 
+// ---- f32 rows -> three bf16 planes h | m | l per row with x == h + m + l (the operands of the plane-walking search frame,
+// sim_tile256_kernel<.., PLANES>, infonce.hip): h = bf16(x), m = bf16(x - h), l = bf16(x - h - m), round to nearest even at each step,
+// each residual formed in f32 (both are exact there: x - h has at most 16 significant bits, x - h - m at most 8).  A thread takes 8
+// consecutive elements of a row: two 16-byte loads, three 16-byte stores; HBM-bound (4 bytes in, 6 out per element).
+// *inexact is raised (a plain store of 1 by every thread that saw one; never cleared here) for an element that is not finite, whose
+// planes do not add up to it in f32, or one of whose planes is a bf16 subnormal: the frame's premise -- every plane normal or zero,
+// so that nothing depends on what the matrix unit does with subnormal inputs -- is checked, not assumed.
+constexpr int kSplitThreads = 256;
+
+__global__ __launch_bounds__(kSplitThreads) void split_bf16x3_kernel(const float* __restrict__ x, int64_t ldx, int64_t rows, int64_t d,
+                                                                     bf16_t* __restrict__ planes, int64_t ldp, int* __restrict__ inexact) {
+    const int64_t vpr = d / 8;                                 // 8-element vectors per row
+    const int64_t nvec = rows * vpr;
+    bool bad = false;
+    for (int64_t v = (int64_t)blockIdx.x * kSplitThreads + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * kSplitThreads) {
+        const int64_t row = v / vpr, col = (v - row * vpr) * 8;
+        const float* src = x + row * ldx + col;
+        const uint4_t a = __builtin_nontemporal_load(reinterpret_cast<const uint4_t*>(src));
+        const uint4_t b = __builtin_nontemporal_load(reinterpret_cast<const uint4_t*>(src + 4));
+        unsigned w[3][8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float xi = __uint_as_float(i < 4 ? a[i] : b[i - 4]);
+            const bf16_t h = f32_to_bf16(xi);
+            const float r1 = xi - bf16_to_f32(h);
+            const bf16_t m = f32_to_bf16(r1);
+            const float r2 = r1 - bf16_to_f32(m);
+            const bf16_t l = f32_to_bf16(r2);
+            w[0][i] = h;
+            w[1][i] = m;
+            w[2][i] = l;
+            const bool sub = ((h & 0x7f80u) == 0 && (h & 0x7fu)) || ((m & 0x7f80u) == 0 && (m & 0x7fu)) || ((l & 0x7f80u) == 0 && (l & 0x7fu));
+            // (a non-finite x fails the comparison: inf - inf and NaN make the sum a NaN)
+            bad |= sub || !(bf16_to_f32(h) + bf16_to_f32(m) + bf16_to_f32(l) == xi) || (__float_as_uint(xi) & 0x7f800000u) == 0x7f800000u;
+        }
+        bf16_t* dst = planes + row * ldp + col;
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl) {
+            uint4_t o;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) o[i] = w[pl][2 * i] | (w[pl][2 * i + 1] << 16);
+            *reinterpret_cast<uint4_t*>(dst + pl * d) = o;
+        }
+    }
+    if (bad) *inexact = 1;
+}
+
 }  // namespace
+
+extern "C" int rpo_split_bf16x3(const float* x, int64_t ldx, int64_t rows, int64_t d, void* planes, int64_t ldp, int32_t* inexact,
+                                rpo_stream_t stream) {
+    if (!x || !planes || !inexact || rows <= 0 || d <= 0 || ldx < d || ldp < 3 * d) return RPO_ERR_INVALID_ARG;
+    if (d % 64 != 0 || ldx % 4 != 0 || ldp % 8 != 0 || !rpo_aligned16(x) || !rpo_aligned16(planes)) return RPO_ERR_UNSUPPORTED;
+    const int64_t nvec = rows * (d / 8);
+    const unsigned grid = (unsigned)std::min<int64_t>(rpo_cdiv(nvec, kSplitThreads), 256 * 32);
+    RPO_LAUNCH(split_bf16x3_kernel, dim3(grid), dim3(kSplitThreads), 0, (hipStream_t)stream, x, ldx, rows, d, (bf16_t*)planes, ldp,
+               (int*)inexact);
+    return rpo_launch_status();
+}
 
 extern "C" int rpo_topk_merge_candidates(const float* cand_val, const int64_t* cand_idx, int32_t* cand_cnt, int64_t rows, int cap,
                                          int k, float* best_val, int64_t* best_idx, int32_t* overflow, rpo_stream_t stream) {

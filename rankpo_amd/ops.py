@@ -1580,7 +1580,89 @@ def search_step(q, p, col0: int, best_val, best_idx, ws: SearchWorkspace, round_
     return best_val, best_idx
 
 
+# ---- the same search on three bf16 planes of f32 operands (an f32 index that is exact in neither 16-bit type) ----
+def split_bf16x3_ref(x):
+    """Pure-torch statement of `split_bf16x3` (works on CPU tensors; what the kernel is tested against): (planes bf16 [..., 3 d] = h | m | l, inexact bool scalar tensor) with
+    h = bf16(x), m = bf16(x - h), l = bf16(x - h - m), round to nearest even, residuals in f32.  inexact: some element is not finite,
+    its planes do not add up to it in f32, or a plane is a bf16 subnormal (the frame's premise is planes that are normal or zero)."""
+    x = x.float()
+    h = x.to(torch.bfloat16)
+    r1 = x - h.float()
+    m = r1.to(torch.bfloat16)
+    r2 = r1 - m.float()
+    l = r2.to(torch.bfloat16)
+    planes = torch.cat([h, m, l], dim=-1)
+    tiny = torch.finfo(torch.bfloat16).tiny                           # 2^-126, the smallest normal (bf16 has f32's exponent range)
+    mag = planes.float().abs()
+    sub = (mag > 0) & (mag < tiny)
+    inexact = (~torch.isfinite(x)).any() | ~((h.float() + m.float() + l.float()) == x).all() | sub.any()
+    return planes, inexact
+
+
+def split_bf16x3(x):
+    """(planes bf16 [rows, 3 d] = h | m | l per row, inexact int32 [1] device flag) of x f32 [rows, d], d % 64 == 0 (rpo_split_bf16x3;
+    in torch: split_bf16x3_ref).  The flag is nonzero when the planes do not represent x exactly; reading it is the caller's sync."""
+    _need_gpu(x)
+    lib = _lib.load()
+    if x.dtype != torch.float32 or x.dim() != 2 or not x.is_contiguous() or x.shape[0] == 0 or x.shape[1] % 64 != 0 or x.data_ptr() % 16:
+        raise ValueError("split_bf16x3: contiguous, 16-byte aligned f32 [rows, d] with rows > 0 and d % 64 == 0")
+    rows, d = x.shape
+    planes = torch.empty((rows, 3 * d), dtype=torch.bfloat16, device=x.device)
+    flag = torch.zeros((1,), dtype=torch.int32, device=x.device)
+    with torch.cuda.device(x.device):
+        check(lib.rpo_split_bf16x3(x.data_ptr(), d, rows, d, planes.data_ptr(), 3 * d, flag.data_ptr(), _stream(x)), "rpo_split_bf16x3")
+    return planes, flag
+
+
+def search_planes_takes(qp, cp) -> bool:
+    """Shapes the plane-walking frame takes: bf16 [rows, 3 d] planes (split_bf16x3), contiguous and 16-byte aligned, of a problem
+    rpo_sim_planes_ok admits: search_filter_takes' shapes applied to d, each operand's planes below 4 GB."""
+    if not (qp.dtype == torch.bfloat16 and cp.dtype == torch.bfloat16 and qp.dim() == 2 and cp.dim() == 2 and qp.is_contiguous()
+            and cp.is_contiguous() and qp.shape[1] == cp.shape[1] and qp.shape[1] % 3 == 0 and qp.data_ptr() % 16 == 0
+            and cp.data_ptr() % 16 == 0):
+        return False
+    return bool(_lib.load().rpo_sim_planes_ok(qp.shape[0], cp.shape[0], qp.shape[1] // 3))
+
+
+def similarity_f32_planes(qp, cp):
+    """f32 scores [Q, P] of f32 operands given as bf16 planes: exact products of the six leading plane pairs, f32 sums in the
+    256 x 256 frame's order, smallest terms first (rpo_sim_scores_f32_planes).  Shapes: search_planes_takes."""
+    _need_gpu(qp, cp)
+    lib = _lib.load()
+    if not search_planes_takes(qp, cp):
+        raise ValueError("similarity_f32_planes: bf16 [rows, 3 d] planes of a shape the plane-walking frame takes (search_planes_takes)")
+    scores = torch.empty((qp.shape[0], cp.shape[0]), dtype=torch.float32, device=qp.device)
+    with torch.cuda.device(qp.device):
+        check(lib.rpo_sim_scores_f32_planes(qp.data_ptr(), cp.data_ptr(), qp.shape[0], cp.shape[0], qp.shape[1] // 3, scores.data_ptr(),
+                                            scores.stride(0), _stream(qp)), "rpo_sim_scores_f32_planes")
+    return scores
+
+
+def search_step_planes(qp, cp, col0: int, best_val, best_idx, ws: SearchWorkspace):
+    """`search_step(round_scores=False)` on planes: rpo_sim_topk_filter_planes + rpo_topk_merge_candidates; the scores are those of
+    `similarity_f32_planes`, bit for bit."""
+    _need_gpu(qp, cp)
+    lib = _lib.load()
+    if not search_planes_takes(qp, cp):
+        raise ValueError("search_step_planes: bf16 [rows, 3 d] planes of a shape the plane-walking frame takes (search_planes_takes)")
+    rows, d = qp.shape[0], qp.shape[1] // 3
+    k = best_val.shape[1]
+    if (ws.rows, ws.k) != (rows, k) or best_val.shape != (rows, k) or best_idx.shape != (rows, k) or not best_val.is_contiguous() \
+            or not best_idx.is_contiguous() or best_val.dtype != torch.float32 or best_idx.dtype != torch.int64:
+        raise ValueError("search_step_planes: best_val / best_idx must be contiguous f32 / int64 [rows, k] matching the workspace")
+    with torch.cuda.device(qp.device):
+        st = _stream(qp)
+        check(lib.rpo_sim_topk_filter_planes(qp.data_ptr(), cp.data_ptr(), rows, cp.shape[0], d, int(col0), k, best_val.data_ptr(),
+                                             best_idx.data_ptr(), ws.cand_val.data_ptr(), ws.cand_idx.data_ptr(), ws.cand_cnt.data_ptr(),
+                                             ws.cap, st), "rpo_sim_topk_filter_planes")
+        check(lib.rpo_topk_merge_candidates(ws.cand_val.data_ptr(), ws.cand_idx.data_ptr(), ws.cand_cnt.data_ptr(), rows, ws.cap, k,
+                                            best_val.data_ptr(), best_idx.data_ptr(), ws.overflow.data_ptr(), st),
+              "rpo_topk_merge_candidates")
+    return best_val, best_idx
+
+
 __all__ = ["sim_gemm_nt", "pool_normalize", "topk_merge", "topk_finish", "search_step", "similarity_f32", "search_filter_takes", "search_filter_ok", "SearchWorkspace",
+           "split_bf16x3", "split_bf16x3_ref", "similarity_f32_planes", "search_step_planes", "search_planes_takes",
            "search_candidate_cap", "linear", "transpose2d", "wgrad", "infonce_loss", "similarity", "rankpo_loss_metrics", "RankPOConfig", "METRIC_KEYS",
            "swiglu_down", "rope_", "fused_encoder_ops_ok", "add_rmsnorm", "fused_norm_ok",
            "flash_attn_varlen", "flash_attn_varlen_qkv", "last_query_attn", "last_query_attn_ok", "rope_flash_attn_varlen_qkv", "rope_flash_attn_varlen_qkv_fwd", "flash_attn_varlen_fwd", "flash_attn_varlen_bwd", "attn_tile_table", "attn_fwd_tile_table", "recomputing",

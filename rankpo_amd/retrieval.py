@@ -42,6 +42,19 @@ def exact_in_bf16(x):
     return exact_in_16(x, torch.bfloat16)
 
 
+def exact_in_planes(x):
+    """x (f32 [rows, d] on the GPU, d % 64 == 0) as three bf16 planes [rows, 3 d] = h | m | l with x == h + m + l (ops.split_bf16x3) if
+    that holds for EVERY value with planes that are normal or zero, else None.  Memory rule of `exact_in_16` (6 bytes per value);
+    one device flag, one sync."""
+    if x.dtype != torch.float32 or not x.is_cuda or x.dim() != 2 or x.numel() == 0 or x.shape[1] % 64 != 0:
+        return None
+    free, _ = torch.cuda.mem_get_info(x.device)
+    if free + torch.cuda.memory_reserved(x.device) - torch.cuda.memory_allocated(x.device) < 6 * x.numel() + (2 << 30):
+        return None
+    planes, inexact = ops.split_bf16x3(x)
+    return None if int(inexact.item()) else planes
+
+
 class FlatIPIndex:
     """Stands where the reference builds `faiss.IndexFlatIP` (utils.py:38-51): keeps the corpus embeddings on the GPU.
 
@@ -49,11 +62,18 @@ class FlatIPIndex:
     over when the encoder computes in bf16, as scripts/evaluate/run_evaluate.sh runs it -- or in fp16 (`use_fp16`, the BGE setup) keeps
     a 16-bit copy (`emb16`) and scores queries that are exact in that type too with the 16-bit MFMA kernel frame: the products are exact in f32 and the sums are f32 sums, i.e.
     an f32 inner product in that kernel's summation order (as FAISS' sgemm has its own), at 16 x the f32 MFMA rate and with the
-    fused filter step.  Scores stay f32, unrounded.  Anything else (values or queries not exact in bf16) takes the f32 kernel."""
+    fused filter step.  Scores stay f32, unrounded.  Anything else (values or queries not exact in bf16) takes the f32 kernel --
+    unless `f32_planes` is set: then an f32 index with d % 64 == 0 that is exact in neither type keeps its values as three bf16 planes
+    (`emb_planes`, [ntotal, 3 d]: x == h + m + l, `exact_in_planes`) and the same frame walks six plane pairs per score, smallest terms
+    first -- exact products, f32 sums in the frame's order, the fused filter step; what it leaves out (the pairs ml, lm, ll) is below
+    2^-23 |q_i c_i| per element, the rounding of an f32 multiply.  ONE value whose planes leave the normal range (non-zero and below
+    ~2^-110 in magnitude, where l turns subnormal) declines the planes for the whole index, silently: check `emb_planes`.
+    Off by default: measured numbers in DESIGN.md."""
 
     candidate_fill = 0.25       # fused search: expected survivors per row and chunk / candidate slots (chunk_schedule)
 
-    def __init__(self, embeddings, device="cuda:0", dtype=torch.float32, chunk_rows: int = 262144, split=None, exact16: bool = True):
+    def __init__(self, embeddings, device="cuda:0", dtype=torch.float32, chunk_rows: int = 262144, split=None, exact16: bool = True,
+                 f32_planes: bool = False):
         e = torch.as_tensor(np.asarray(embeddings, dtype=np.float32) if not torch.is_tensor(embeddings) else embeddings)
         self.emb = e.to(device=device, dtype=dtype).contiguous()
         self.ntotal = self.emb.shape[0]
@@ -71,6 +91,8 @@ class FlatIPIndex:
             self.emb16 = exact_in_16(self.emb, torch.bfloat16)
             if self.emb16 is None:
                 self.emb16 = exact_in_16(self.emb, torch.float16)
+        # f32 index exact in neither 16-bit type, on request: three bf16 planes (class docstring); None: nothing changes
+        self.emb_planes = exact_in_planes(self.emb) if f32_planes and self.emb16 is None else None
 
     def chunk_schedule(self, nq: int, k: int, fused: bool = True):
         """[(first row, end row)] of the corpus chunks a search of nq query rows walks.  Plain: `chunk_rows` at a time.  Fused: the
@@ -80,17 +102,23 @@ class FlatIPIndex:
         quarter of the candidate list (`candidate_fill`: 2.56 c at k = 100; at k = 1024, where the lists hold 3 k, never below the
         first chunk's size, i.e. a third of the list), up to chunk_rows.  Measured at 10^6 x 2048, 1024 queries, k = 100: lists
         1/8, 1/4, 1/2 full 3.86 / 3.82 / 3.85 ms (gpurun_out/r6_N) -- a chunk with more survivors pays for them in the filter's
-        epilogue what it saves in launches.  A tail too small for the kernel is joined to the last chunk."""
-        plain = [(c0, min(c0 + self.chunk_rows, self.ntotal)) for c0 in range(0, self.ntotal, self.chunk_rows)]
-        if not fused or not (self.emb.dtype == torch.bfloat16 or getattr(self, "emb16", None) is not None) or nq <= 0:
+        epilogue what it saves in launches.  A tail too small for the kernel is joined to the last chunk.
+        An index that holds `emb_planes` cuts every schedule -- also that of a search which falls through to the f32 kernel -- so
+        that a chunk's planes stay below 4 GB: below the default chunk_rows only for d > 2730."""
+        chunk_rows = self.chunk_rows
+        planes = getattr(self, "emb_planes", None) is not None
+        if planes:                                                  # a chunk's planes (6 d bytes per row) stay below 4 GB: 32-bit piece offsets
+            chunk_rows = max(256, min(chunk_rows, ((1 << 32) - 1) // (6 * self.emb.shape[1]) // 256 * 256))
+        plain = [(c0, min(c0 + chunk_rows, self.ntotal)) for c0 in range(0, self.ntotal, chunk_rows)]
+        if not fused or not (self.emb.dtype == torch.bfloat16 or getattr(self, "emb16", None) is not None or planes) or nq <= 0:
             return plain
         first = max(-(-192 // -(-nq // 256)), -(-k // 256)) * 256
-        if 2 * first > min(self.chunk_rows, self.ntotal) or not ops.search_filter_ok(nq, first, self.emb.shape[1]):
+        if 2 * first > min(chunk_rows, self.ntotal) or not ops.search_filter_ok(nq, first, self.emb.shape[1]):
             return plain
         out, c = [(0, first)], first
         while c < self.ntotal:
             n = max(first, int(c * ops.search_candidate_cap(k) * self.candidate_fill / k) // 256 * 256)
-            n = min(n, self.chunk_rows, self.ntotal - c)
+            n = min(n, chunk_rows, self.ntotal - c)
             if self.ntotal - (c + n) < first:
                 n = self.ntotal - c
             out.append((c, c + n))
@@ -114,6 +142,10 @@ class FlatIPIndex:
         # 1024 queries), no second pass over it.  A candidate list that runs over (a corpus whose later rows keep beating everything
         # before them) raises the workspace's flag and the search is redone the plain way.
         fused = self.fused and split == 1
+        if getattr(self, "emb_planes", None) is not None:
+            out = self._search_planes(q, k, split, fused)
+            if out is not None:
+                return out
         # f32 index exact in bf16 + queries exact in bf16: the bf16 kernel frame with f32 scores (class docstring)
         q16 = exact_in_16(q, self.emb16.dtype) if self.emb16 is not None and q.shape[0] > 0 else None
         frame = q16 is not None or self.emb.dtype == torch.bfloat16
@@ -139,10 +171,41 @@ class FlatIPIndex:
                 self.fused = saved
         return ops.topk_finish(top, idx, split)
 
+    def _search_planes(self, q, k, split, fused):
+        """search() on `emb_planes`: the queries are split per call; None (the caller goes on to the f32 kernel) when they are not exact
+        in three planes or a chunk is not of a shape the plane frame takes.  The chunks are those of the fused schedule either way; the
+        first goes through the frame's score matrix + topk_merge, the later ones through the fused step (fused) or the score matrix too,
+        so every score of a search comes out of one summation order.  A candidate overflow redoes the walk through the score matrix."""
+        if q.shape[0] == 0 or q.shape[1] != self.emb.shape[1]:
+            return None
+        qp, inexact = ops.split_bf16x3(q)
+        if int(inexact.item()):
+            return None
+        sched = self.chunk_schedule(q.shape[0], k, True)
+        if not all(ops.search_planes_takes(qp, self.emb_planes[c0:c1]) for c0, c1 in sched):
+            return None
 
-def create_faiss_index(embeddings, device="cuda:0"):
-    """Name kept from the reference (utils.py:38)."""
-    return FlatIPIndex(embeddings, device=device)
+        def walk(fused):
+            top = idx = ws = None
+            for c0, c1 in sched:
+                if fused and c0 >= k:
+                    ws = ws or ops.SearchWorkspace(q.shape[0], k, q.device)
+                    ops.search_step_planes(qp, self.emb_planes[c0:c1], c0, top, idx, ws)
+                    continue
+                scores = ops.similarity_f32_planes(qp, self.emb_planes[c0:c1])
+                top, idx = ops.topk_merge(scores, c0, top, idx, k, split=split)
+            return top, idx, ws
+
+        top, idx, ws = walk(fused)
+        if ws is not None and int(ws.overflow.item()):
+            self.fused_overflows += 1
+            top, idx, _ = walk(False)
+        return ops.topk_finish(top, idx, split)
+
+
+def create_faiss_index(embeddings, device="cuda:0", f32_planes: bool = False):
+    """Name kept from the reference (utils.py:38).  f32_planes: FlatIPIndex's opt-in plane frame for f32 embeddings."""
+    return FlatIPIndex(embeddings, device=device, f32_planes=f32_planes)
 
 
 def faiss_search(index: FlatIPIndex, query_embedding, topk: int = 100, batch_size: int = 256):

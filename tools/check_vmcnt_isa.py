@@ -35,7 +35,8 @@ SIG_FILE = os.path.join(HERE, "isa_signatures.json")
 # kernel name substring -> Q pieces per wave (64 rows x row bytes / 1 KiB pieces / 4 waves ... = what the source calls QP_)
 PROLOGUE = {"fa_fwd128w_kernel": 16, "fa_fwd64w_kernel": 8}
 SIGNED = {"attention.s": ["fa_fwd128w_kernel", "fa_fwd64w_kernel", "fa_bwd_dkdv4_kernel", "fa_bwd_dkdv128_kernel", "fa_bwd_dq64w_kernel"],
-          "infonce.s": ["sim_tile256_kernel"]}
+          # (all instances; and the two plane-walking ones -- <EPI 3 / 4, bf16, PLANES> -- on their own)
+          "infonce.s": ["sim_tile256_kernel", "sim_tile256_kernelILi3ELb0ELb1E", "sim_tile256_kernelILi4ELb0ELb1E"]}
 
 OPTIONAL = ("fa_fwd64w_kernel", "fa_bwd_dq64w_kernel")     # only in a `make ONEWAVE64=1` build (rpo_build_flags())
 
