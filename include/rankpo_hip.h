@@ -484,6 +484,39 @@ int rpo_gelu_bwd(const void* u, int64_t ldu, const void* dh, int64_t lddh, void*
                  int dtype, rpo_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * (10b) hidden-state dropout inside the row kernels of (10) (opt-in: encoder.BERT_FUSED_HIDDEN_DROPOUT, and what gradient
+ * checkpointing on the packed step recomputes).  keep(seed, site, row, column) is the attention dropout's function with (site, row,
+ * column) in the places of (head, query row, key row): Philox2x32-10, counter = (row, column >> 2), key = the 32-bit mix of seed and
+ * site, one 16-bit field per column of a group of 4, kept when field >= round(p_drop * 65536).  "row" = the row index in the tensors
+ * passed to the call.  Stateless: the backward and a recomputed forward evaluate it again.  The caller passes a seed that no
+ * attention call of the step uses (ops.bert_hidden_seed).  0 <= p_drop < 1; p_drop < 2^-17 drops nothing and scales nothing.
+ * inv_keep = rpo_hidden_dropout_scale(p_drop) = 1 / (1 - p_drop) in f32, the attention kernels' factor.  drop(x) below =
+ * round(f32(x) * inv_keep) * keep on a value x of the storage type: the rounding points of a separate dropout pass.
+ * bf16 / fp16, d % 8 == 0, d <= 4096, strides % 8 == 0, 16-byte aligned, rows <= 2^31 - 1; rows == 0 does nothing.
+ *
+ * rpo_add_layernorm_drop_fwd: s = round(a + drop(b)) (b required), y = LayerNorm(s); s stored as rpo_add_layernorm_train_fwd does.
+ * rpo_bert_embed_ln_drop_fwd: s as rpo_bert_embed_ln_train_fwd, y = drop(round(LayerNorm(s))).
+ * rpo_layernorm_drop_bwd: rpo_layernorm_bwd (the same partials in the same order) with site_in >= 0: dy <- drop(dy) with site_in as
+ * it is loaded (the backward of rpo_bert_embed_ln_drop_fwd); db != NULL: db = drop(round(ds)) with site_out written beside ds (the
+ * backward of rpo_add_layernorm_drop_fwd: ds is the gradient of a, db that of b).  A negative site switches its side off.
+ * rpo_hidden_dropout_mask: mask[i][c] (uint8, 1 = kept) for rows row0 + i < row0 + rows, columns c < d.  Tests and diagnostics only.
+ * --------------------------------------------------------------------------------------------- */
+float rpo_hidden_dropout_scale(float p_drop);   /* 0 for p_drop outside [0, 1) */
+int rpo_add_layernorm_drop_fwd(const void* a, int64_t lda, const void* b, int64_t ldb, const void* gamma, const void* beta,
+                               float eps, void* y, int64_t ldy, void* s, int64_t lds, int64_t rows, int64_t d, int dtype,
+                               float p_drop, uint64_t seed, int64_t site, rpo_stream_t stream);
+int rpo_bert_embed_ln_drop_fwd(const int* ids, const int* token_types, const int* pos, int64_t tokens, const void* word,
+                               int64_t vocab, const void* type_emb, int64_t n_types, const void* pos_emb, int64_t n_pos,
+                               const void* gamma, const void* beta, float eps, void* y, int64_t ldy, void* s, int64_t lds,
+                               int64_t d, int dtype, float p_drop, uint64_t seed, int64_t site, rpo_stream_t stream);
+int rpo_layernorm_drop_bwd(const void* s, int64_t lds, const void* gamma, const void* dy, int64_t lddy, float eps, void* ds,
+                           int64_t ldds, void* db, int64_t lddb, float* dgamma_partial, float* dbeta_partial, int64_t rows,
+                           int64_t d, int dtype, float p_drop, uint64_t seed, int64_t site_in, int64_t site_out,
+                           rpo_stream_t stream);
+int rpo_hidden_dropout_mask(int64_t row0, int64_t rows, int64_t d, float p_drop, uint64_t seed, int64_t site,
+                            unsigned char* mask, rpo_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * (8) exact top-k over score rows, merged chunk by chunk ("next" row f3: the k-selection of faiss.IndexFlatIP.search,
  * reference src/utils.py:58-80).  scores: [rows, cols] (row stride ld elements) of the chunk whose first column is corpus
  * row col0; best_val f32 [rows, k] / best_idx int64 [rows, k]: the winners so far, best first (value descending, ties by

@@ -107,6 +107,14 @@ SIGNATURES = {
     "rpo_layernorm_bwd": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _f32, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp]),
     "rpo_gelu_out_fwd": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp]),
     "rpo_gelu_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp]),
+    "rpo_hidden_dropout_scale": (_f32, [_f32]),
+    "rpo_add_layernorm_drop_fwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _f32, _vp, _i64, _vp, _i64, _i64, _i64, _i32, _f32, _u64,
+                                             _i64, _vp]),
+    "rpo_bert_embed_ln_drop_fwd": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _f32, _vp, _i64, _vp,
+                                             _i64, _i64, _i32, _f32, _u64, _i64, _vp]),
+    "rpo_layernorm_drop_bwd": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _f32, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _f32,
+                                         _u64, _i64, _i64, _vp]),
+    "rpo_hidden_dropout_mask": (C.c_int, [_i64, _i64, _i64, _f32, _u64, _i64, _vp, _vp]),
 }
 
 _lib = None

@@ -13,6 +13,9 @@
 //   rpo_add_layernorm_train_fwd / rpo_bert_embed_ln_train_fwd   the forwards, also storing the rounded sum s
 //   rpo_layernorm_bwd            ds and per-block dgamma / dbeta partials from s, gamma and dy
 //   rpo_gelu_out_fwd / rpo_gelu_bwd   out-of-place GELU and its derivative
+// and, opt-in, the hidden-state dropout inside the row kernels (what gradient checkpointing on the packed step recomputes):
+//   rpo_add_layernorm_drop_fwd / rpo_bert_embed_ln_drop_fwd / rpo_layernorm_drop_bwd   the three row kernels with a stateless keep
+//   rpo_hidden_dropout_mask / rpo_hidden_dropout_scale                                 that keep function and its scale (tests)
 // Plain HIP with MFMA builtins; no inline asm, no counted waits.  No atomics: every entry is deterministic.
 #include "common.hpp"
 
@@ -1202,5 +1205,377 @@ extern "C" int rpo_gelu_bwd(const void* u, int64_t ldu, const void* dh, int64_t 
         RPO_LAUNCH(gelu_bwd_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)u, ldu, (const bf16_t*)dh, lddh, (bf16_t*)du, lddu, rows, cols);
     else
         RPO_LAUNCH(gelu_bwd_kernel<f16_t>, grid, block, 0, st, (const f16_t*)u, ldu, (const f16_t*)dh, lddh, (f16_t*)du, lddu, rows, cols);
+    return rpo_launch_status();
+}
+
+// ---- hidden-state dropout inside the row kernels ---------------------------------------------------------
+// keep(seed, site, packed row, column): the attention dropout's stateless function with (site, row, column) in the places of
+// (head, query row, key row): key = dropout_key(seed, site), bits = dropout_bits(key, row, column >> 2), one 16-bit field per
+// column of the group of 4, KEPT when field >= thr = round(p_drop * 65536).  A lane's 16-byte vector (8 columns) takes two Philox
+// evaluations.  site 0 = the embedding output, 1 + 2 i / 2 + 2 i = the two `dropout(dense(..))` of block i; the seed is
+// ops.bert_hidden_seed(call seed), which no block's attention seed equals.  A recomputed forward (gradient checkpointing) and the
+// backward evaluate the function again: no mask is stored and no generator state is kept.
+// Rounding points are those of the unfused path, x -> round(f32(x) * inv_keep) * keep on stored values: the dense output before
+// the add (add + LayerNorm), the ROUNDED LayerNorm output (embedding), the rounded ds (backward, towards the dense output).
+// These are kernels of their own beside add_layernorm_kernel / bert_embed_ln_kernel / layernorm_bwd_kernel, which stay as they are.
+namespace {
+
+__device__ __forceinline__ bool hidden_keep(uint64_t seed, int site, int row, int col, unsigned thr) {
+    return dropout_field_keep(dropout_bits(dropout_key(seed, site), row, col >> 2), col, thr);
+}
+// t <- round(t * inv_keep) * keep for the 8 columns c0 .. c0 + 7 (c0 % 8 == 0) of one row; key = dropout_key(seed, site)
+template <typename T>
+__device__ __forceinline__ void hidden_drop8(Vec16<T>& t, unsigned key, int row, int c0, unsigned thr, float inv_keep) {
+    const DropBits lo = dropout_bits(key, row, c0 >> 2), hi = dropout_bits(key, row, (c0 >> 2) + 1);
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+        t.v[e] = Elem<T>::round(t.v[e] * inv_keep) * (dropout_field_keep(e < 4 ? lo : hi, c0 + e, thr) ? 1.f : 0.f);
+}
+
+// layernorm_store's arithmetic, the f32 results left in x (not stored)
+template <typename T, int NV>
+__device__ __forceinline__ void layernorm_rows(Vec16<T> (&x)[NV], const T* __restrict__ gamma, const T* __restrict__ beta,
+                                               float eps, int d, int lane) {
+    float sum = 0.f;
+#pragma unroll
+    for (int j = 0; j < NV; ++j)
+        if (8 * (lane + 64 * j) < d)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) sum += x[j].v[e];
+    const float mean = wave_sum(sum) / (float)d;
+    float sq = 0.f;
+#pragma unroll
+    for (int j = 0; j < NV; ++j)
+        if (8 * (lane + 64 * j) < d)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float c = x[j].v[e] - mean;
+                sq = fmaf(c, c, sq);
+            }
+    const float rstd = rsqrtf(wave_sum(sq) / (float)d + eps);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int c0 = 8 * (lane + 64 * j);
+        if (c0 < d) {
+            Vec16<T> gw, bw;
+            gw.load(gamma + c0);
+            bw.load(beta + c0);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) x[j].v[e] = fmaf((x[j].v[e] - mean) * rstd, gw.v[e], bw.v[e]);
+        }
+    }
+}
+
+// s = round(a + round(b * inv_keep) * keep), y = LayerNorm(s); s stored for the backward
+template <typename T, int NV>
+__global__ __launch_bounds__(kRowThreads) void add_layernorm_drop_kernel(const T* __restrict__ a, int64_t lda, const T* __restrict__ b,
+                                                                          int64_t ldb, const T* __restrict__ gamma,
+                                                                          const T* __restrict__ beta, float eps, T* __restrict__ y,
+                                                                          int64_t ldy, T* __restrict__ s_out, int64_t lds,
+                                                                          int64_t rows, int d, unsigned thr, float inv_keep,
+                                                                          uint64_t seed, int site) {
+    const int64_t row = (int64_t)blockIdx.x * (kRowThreads / 64) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const unsigned key = dropout_key(seed, site);
+    Vec16<T> x[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int c0 = 8 * (lane + 64 * j);
+        if (c0 < d) {
+            Vec16<T> t;
+            x[j].load(a + row * lda + c0);
+            t.load(b + row * ldb + c0);
+            hidden_drop8<T>(t, key, (int)row, c0, thr, inv_keep);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) x[j].v[e] = Elem<T>::round(x[j].v[e] + t.v[e]);
+            x[j].store(s_out + row * lds + c0);
+        }
+    }
+    layernorm_rows<T, NV>(x, gamma, beta, eps, d, lane);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int c0 = 8 * (lane + 64 * j);
+        if (c0 < d) x[j].store(y + row * ldy + c0);
+    }
+}
+
+// bert_embed_ln_kernel with y = round(round(LayerNorm(s)) * inv_keep) * keep
+template <typename T, int NV>
+__global__ __launch_bounds__(kRowThreads) void bert_embed_ln_drop_kernel(
+    const int* __restrict__ ids, const int* __restrict__ tts, const int* __restrict__ pos, int64_t tokens,
+    const T* __restrict__ word, int64_t vocab, const T* __restrict__ temb, int64_t ntypes, const T* __restrict__ pemb,
+    int64_t npos, const T* __restrict__ gamma, const T* __restrict__ beta, float eps, T* __restrict__ y, int64_t ldy,
+    T* __restrict__ s_out, int64_t lds, int d, unsigned thr, float inv_keep, uint64_t seed, int site) {
+    const int64_t row = (int64_t)blockIdx.x * (kRowThreads / 64) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= tokens) return;
+    const int64_t wi = clamp_index(ids[row], vocab);            // clamped into their tables, as bert_embed_ln_kernel
+    const int64_t ti = tts ? clamp_index(tts[row], ntypes) : 0;
+    const int64_t pi = clamp_index(pos[row], npos);
+    const unsigned key = dropout_key(seed, site);
+    Vec16<T> x[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int c0 = 8 * (lane + 64 * j);
+        if (c0 < d) {
+            Vec16<T> t, p;
+            x[j].load(word + wi * d + c0);
+            t.load(temb + ti * d + c0);
+            p.load(pemb + pi * d + c0);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) x[j].v[e] = Elem<T>::round(Elem<T>::round(x[j].v[e] + t.v[e]) + p.v[e]);   // (w + t) + p
+            x[j].store(s_out + row * lds + c0);
+        }
+    }
+    layernorm_rows<T, NV>(x, gamma, beta, eps, d, lane);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int c0 = 8 * (lane + 64 * j);
+        if (c0 < d) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) x[j].v[e] = Elem<T>::round(x[j].v[e]);       // the LayerNorm output as it would be stored
+            hidden_drop8<T>(x[j], key, (int)row, c0, thr, inv_keep);
+            x[j].store(y + row * ldy + c0);
+        }
+    }
+}
+
+// layernorm_bwd_kernel (same rows per wave, same summation order of the dgamma / dbeta partials) with the dropout of the fused
+// forwards: site_in >= 0: dy <- round(dy * inv_keep) * keep(site_in) as it is loaded (the embedding: dropout AFTER the LayerNorm);
+// db != nullptr: db = round(round(ds) * inv_keep) * keep(site_out) beside ds (add + LayerNorm: ds to a, db to the dense output b).
+template <typename T, int NV>
+__global__ __launch_bounds__(64 * kLnBwdWaves) void layernorm_drop_bwd_kernel(
+    const T* __restrict__ s, int64_t lds, const T* __restrict__ gamma, const T* __restrict__ dy, int64_t lddy, float eps,
+    T* __restrict__ ds, int64_t ldds, T* __restrict__ db_out, int64_t lddb, float* __restrict__ dgp, float* __restrict__ dbp,
+    int64_t rows, int d, unsigned thr, float inv_keep, uint64_t seed, int site_in, int site_out) {
+    extern __shared__ float ln_red[];       // [2][d]: the block's dgamma | dbeta sums
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned key_in = dropout_key(seed, site_in), key_out = dropout_key(seed, site_out);
+    float dg[NV][8], db[NV][8];
+    Vec16<T> gw[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dg[j][e] = db[j][e] = 0.f;
+        if (8 * (lane + 64 * j) < d) gw[j].load(gamma + 8 * (lane + 64 * j));
+    }
+    for (int64_t row = (int64_t)blockIdx.x * kLnBwdWaves + wave; row < rows; row += (int64_t)gridDim.x * kLnBwdWaves) {
+        Vec16<T> x[NV], g[NV];
+        float sum = 0.f;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int c0 = 8 * (lane + 64 * j);
+            if (c0 < d) {
+                x[j].load(s + row * lds + c0);
+                g[j].load(dy + row * lddy + c0);
+                if (site_in >= 0) hidden_drop8<T>(g[j], key_in, (int)row, c0, thr, inv_keep);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) sum += x[j].v[e];
+            }
+        }
+        const float mean = wave_sum(sum) / (float)d;
+        float sq = 0.f;
+#pragma unroll
+        for (int j = 0; j < NV; ++j)
+            if (8 * (lane + 64 * j) < d)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float c = x[j].v[e] - mean;
+                    sq = fmaf(c, c, sq);
+                }
+        const float rstd = rsqrtf(wave_sum(sq) / (float)d + eps);
+        float c1 = 0.f, c2 = 0.f;
+#pragma unroll
+        for (int j = 0; j < NV; ++j)
+            if (8 * (lane + 64 * j) < d)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float xh = (x[j].v[e] - mean) * rstd, dyv = g[j].v[e], gg = dyv * gw[j].v[e];
+                    dg[j][e] = fmaf(dyv, xh, dg[j][e]);
+                    db[j][e] += dyv;
+                    x[j].v[e] = xh;
+                    g[j].v[e] = gg;
+                    c1 += gg;
+                    c2 = fmaf(gg, xh, c2);
+                }
+        c1 = wave_sum(c1) / (float)d;
+        c2 = wave_sum(c2) / (float)d;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int c0 = 8 * (lane + 64 * j);
+            if (c0 < d) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) g[j].v[e] = rstd * (g[j].v[e] - c1 - x[j].v[e] * c2);
+                g[j].store(ds + row * ldds + c0);
+                if (db_out) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) g[j].v[e] = Elem<T>::round(g[j].v[e]);      // ds as stored
+                    hidden_drop8<T>(g[j], key_out, (int)row, c0, thr, inv_keep);
+                    g[j].store(db_out + row * lddb + c0);
+                }
+            }
+        }
+    }
+    for (int w = 0; w < kLnBwdWaves; ++w) {
+        if (wave == w) {
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+                const int c0 = 8 * (lane + 64 * j);
+                if (c0 < d) {
+                    float* gl = ln_red + c0;
+                    float* bl = ln_red + d + c0;
+                    float* gp = dgp + (int64_t)blockIdx.x * d + c0;
+                    float* bp = dbp + (int64_t)blockIdx.x * d + c0;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const float a = w == 0 ? dg[j][e] : gl[e] + dg[j][e];
+                        const float b = w == 0 ? db[j][e] : bl[e] + db[j][e];
+                        if (w == kLnBwdWaves - 1) {
+                            gp[e] = a;
+                            bp[e] = b;
+                        } else {
+                            gl[e] = a;
+                            bl[e] = b;
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// the keep mask of rows row0 .. row0 + rows - 1, columns 0 .. d - 1 of one site: mask[row][column] (tests and diagnostics)
+__global__ __launch_bounds__(256) void hidden_dropout_mask_kernel(int row0, int rows, int d, int site, unsigned thr, uint64_t seed,
+                                                                  unsigned char* __restrict__ mask) {
+    const int64_t n = (int64_t)rows * d;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        mask[i] = hidden_keep(seed, site, row0 + (int)(i / d), (int)(i % d), thr) ? 1 : 0;
+}
+
+constexpr int64_t kHiddenMaxSite = 1 << 20;     // a site is a small layer index; the bound only keeps it an int
+
+// thr / inv_keep of the kernels: p_drop below 2^-17 quantises to thr = 0 = no dropout, and then nothing is scaled either
+bool hidden_dropout_args(float p_drop, unsigned* thr, float* inv_keep) {
+    if (!dropout_args(p_drop, thr, inv_keep)) return false;
+    if (*thr == 0) *inv_keep = 1.0f;
+    return true;
+}
+
+}  // namespace
+
+extern "C" float rpo_hidden_dropout_scale(float p_drop) {
+    unsigned thr;
+    float inv_keep;
+    return hidden_dropout_args(p_drop, &thr, &inv_keep) ? inv_keep : 0.0f;
+}
+
+extern "C" int rpo_add_layernorm_drop_fwd(const void* a, int64_t lda, const void* b, int64_t ldb, const void* gamma,
+                                          const void* beta, float eps, void* y, int64_t ldy, void* s, int64_t lds, int64_t rows,
+                                          int64_t d, int dtype, float p_drop, uint64_t seed, int64_t site, rpo_stream_t stream) {
+    unsigned thr;
+    float inv_keep;
+    if (!a || !b || !gamma || !beta || !y || !s || rows < 0 || rows > 0x7fffffff || d <= 0 || !rpo_dtype_ok(dtype) || lda < d ||
+        ldb < d || ldy < d || lds < d || site < 0 || site > kHiddenMaxSite || !hidden_dropout_args(p_drop, &thr, &inv_keep))
+        return RPO_ERR_INVALID_ARG;
+    const int nv = row_vectors(d);
+    if (dtype == RPO_DT_F32 || d % 8 || nv == 0) return RPO_ERR_UNSUPPORTED;
+    if (!rpo_aligned16(a) || !rpo_aligned16(b) || !rpo_aligned16(gamma) || !rpo_aligned16(beta) || !rpo_aligned16(y) ||
+        !rpo_aligned16(s) || lda % 8 || ldb % 8 || ldy % 8 || lds % 8)
+        return RPO_ERR_UNSUPPORTED;
+    if (rows == 0) return RPO_OK;
+    const dim3 grid((unsigned)rpo_cdiv(rows, kRowThreads / 64));
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == RPO_DT_BF16)
+        RPO_ROW_DISPATCH(add_layernorm_drop_kernel, bf16_t, nv, grid, st, (const bf16_t*)a, lda, (const bf16_t*)b, ldb,
+                         (const bf16_t*)gamma, (const bf16_t*)beta, eps, (bf16_t*)y, ldy, (bf16_t*)s, lds, rows, (int)d, thr,
+                         inv_keep, seed, (int)site);
+    else
+        RPO_ROW_DISPATCH(add_layernorm_drop_kernel, f16_t, nv, grid, st, (const f16_t*)a, lda, (const f16_t*)b, ldb,
+                         (const f16_t*)gamma, (const f16_t*)beta, eps, (f16_t*)y, ldy, (f16_t*)s, lds, rows, (int)d, thr,
+                         inv_keep, seed, (int)site);
+    return rpo_launch_status();
+}
+
+extern "C" int rpo_bert_embed_ln_drop_fwd(const int* ids, const int* token_types, const int* pos, int64_t tokens,
+                                          const void* word, int64_t vocab, const void* type_emb, int64_t n_types,
+                                          const void* pos_emb, int64_t n_pos, const void* gamma, const void* beta, float eps,
+                                          void* y, int64_t ldy, void* s, int64_t lds, int64_t d, int dtype, float p_drop,
+                                          uint64_t seed, int64_t site, rpo_stream_t stream) {
+    unsigned thr;
+    float inv_keep;
+    if (!ids || !pos || !word || !type_emb || !pos_emb || !gamma || !beta || !y || !s || tokens < 0 || tokens > 0x7fffffff ||
+        vocab <= 0 || n_types <= 0 || n_pos <= 0 || d <= 0 || ldy < d || lds < d || !rpo_dtype_ok(dtype) || site < 0 ||
+        site > kHiddenMaxSite || !hidden_dropout_args(p_drop, &thr, &inv_keep))
+        return RPO_ERR_INVALID_ARG;
+    const int nv = row_vectors(d);
+    if (dtype == RPO_DT_F32 || d % 8 || nv == 0 || ldy % 8 || lds % 8) return RPO_ERR_UNSUPPORTED;
+    if (!rpo_aligned16(word) || !rpo_aligned16(type_emb) || !rpo_aligned16(pos_emb) || !rpo_aligned16(gamma) ||
+        !rpo_aligned16(beta) || !rpo_aligned16(y) || !rpo_aligned16(s))
+        return RPO_ERR_UNSUPPORTED;
+    if (tokens == 0) return RPO_OK;
+    const dim3 grid((unsigned)rpo_cdiv(tokens, kRowThreads / 64));
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == RPO_DT_BF16)
+        RPO_ROW_DISPATCH(bert_embed_ln_drop_kernel, bf16_t, nv, grid, st, ids, token_types, pos, tokens, (const bf16_t*)word, vocab,
+                         (const bf16_t*)type_emb, n_types, (const bf16_t*)pos_emb, n_pos, (const bf16_t*)gamma,
+                         (const bf16_t*)beta, eps, (bf16_t*)y, ldy, (bf16_t*)s, lds, (int)d, thr, inv_keep, seed, (int)site);
+    else
+        RPO_ROW_DISPATCH(bert_embed_ln_drop_kernel, f16_t, nv, grid, st, ids, token_types, pos, tokens, (const f16_t*)word, vocab,
+                         (const f16_t*)type_emb, n_types, (const f16_t*)pos_emb, n_pos, (const f16_t*)gamma,
+                         (const f16_t*)beta, eps, (f16_t*)y, ldy, (f16_t*)s, lds, (int)d, thr, inv_keep, seed, (int)site);
+    return rpo_launch_status();
+}
+
+extern "C" int rpo_layernorm_drop_bwd(const void* s, int64_t lds, const void* gamma, const void* dy, int64_t lddy, float eps,
+                                      void* ds, int64_t ldds, void* db, int64_t lddb, float* dgamma_partial, float* dbeta_partial,
+                                      int64_t rows, int64_t d, int dtype, float p_drop, uint64_t seed, int64_t site_in,
+                                      int64_t site_out, rpo_stream_t stream) {
+    unsigned thr;
+    float inv_keep;
+    if (!s || !gamma || !dy || !ds || !dgamma_partial || !dbeta_partial || rows < 0 || rows > 0x7fffffff || d <= 0 ||
+        !rpo_dtype_ok(dtype) || lds < d || lddy < d || ldds < d || (db && lddb < d) || site_in > kHiddenMaxSite ||
+        site_out > kHiddenMaxSite || (db && site_out < 0) || !hidden_dropout_args(p_drop, &thr, &inv_keep))
+        return RPO_ERR_INVALID_ARG;
+    const int nv = row_vectors(d);
+    if (dtype == RPO_DT_F32 || d % 8 || nv == 0) return RPO_ERR_UNSUPPORTED;
+    if (!rpo_aligned16(s) || !rpo_aligned16(gamma) || !rpo_aligned16(dy) || !rpo_aligned16(ds) || (db && !rpo_aligned16(db)) ||
+        lds % 8 || lddy % 8 || ldds % 8 || (db && lddb % 8))
+        return RPO_ERR_UNSUPPORTED;
+    if (rows == 0) return RPO_OK;               // nothing is written: the caller's partials stay as they are
+    const dim3 grid((unsigned)rpo_layernorm_bwd_blocks(rows)), block(64 * kLnBwdWaves);
+    const size_t red_bytes = 2 * (size_t)d * sizeof(float);     // <= 32 KiB (d <= 4096)
+    hipStream_t st = (hipStream_t)stream;
+    const int si = site_in < 0 ? -1 : (int)site_in, so = site_out < 0 ? 0 : (int)site_out;
+#define RPO_LN_DROP_BWD(T, NV)                                                                                                \
+    RPO_LAUNCH((layernorm_drop_bwd_kernel<T, NV>), grid, block, red_bytes, st, (const T*)s, lds, (const T*)gamma, (const T*)dy,  \
+               lddy, eps, (T*)ds, ldds, (T*)db, lddb, dgamma_partial, dbeta_partial, rows, (int)d, thr, inv_keep, seed, si, so)
+#define RPO_LN_DROP_BWD_T(T)                       \
+    do {                                           \
+        if (nv == 1) RPO_LN_DROP_BWD(T, 1);        \
+        else if (nv == 2) RPO_LN_DROP_BWD(T, 2);   \
+        else if (nv == 4) RPO_LN_DROP_BWD(T, 4);   \
+        else RPO_LN_DROP_BWD(T, 8);                \
+    } while (0)
+    if (dtype == RPO_DT_BF16) RPO_LN_DROP_BWD_T(bf16_t);
+    else RPO_LN_DROP_BWD_T(f16_t);
+#undef RPO_LN_DROP_BWD_T
+#undef RPO_LN_DROP_BWD
+    return rpo_launch_status();
+}
+
+extern "C" int rpo_hidden_dropout_mask(int64_t row0, int64_t rows, int64_t d, float p_drop, uint64_t seed, int64_t site,
+                                       unsigned char* mask, rpo_stream_t stream) {
+    unsigned thr;
+    float inv_keep;
+    if (!mask || row0 < 0 || rows < 0 || d < 0 || row0 + rows > 0x7fffffff || d > 0x7fffffff || site < 0 ||
+        site > kHiddenMaxSite || !hidden_dropout_args(p_drop, &thr, &inv_keep))
+        return RPO_ERR_INVALID_ARG;
+    const int64_t n = rows * d;
+    if (n == 0) return RPO_OK;
+    const int64_t nb = rpo_cdiv(n, 256);
+    RPO_LAUNCH(hidden_dropout_mask_kernel, dim3((unsigned)(nb < 65536 ? nb : 65536)), dim3(256), 0, (hipStream_t)stream,
+               (int)row0, (int)rows, (int)d, (int)site, thr, seed, mask);
     return rpo_launch_status();
 }

@@ -15,6 +15,7 @@ MI355X notes
 """
 from __future__ import annotations
 
+import functools
 import json
 import math
 import os
@@ -795,7 +796,8 @@ class BertEncoder(nn.Module):
         self.embeddings = BertEmbeddings(config)
         self.encoder = _BertStack(config)
         self.gradient_checkpointing = False
-        self.last_dropout_seed = None          # attention-dropout seed of the latest `pooled_cls_train` call (tests read it)
+        self.checkpoint_packed = False         # gradient_checkpointing_enable(packed=True): checkpoint the blocks of the packed step
+        self.last_dropout_seed = None          # dropout seed of the latest `pooled_cls_train` call (tests read it)
         self.apply(self._init)
 
     def _init(self, m):
@@ -809,8 +811,14 @@ class BertEncoder(nn.Module):
                 with torch.no_grad():
                     m.weight[m.padding_idx].zero_()
 
-    def gradient_checkpointing_enable(self, **_):
+    def gradient_checkpointing_enable(self, packed: bool = False, gradient_checkpointing_kwargs=None, **_):
+        """The reference's `--gradient_checkpointing`.  The bare call checkpoints the blocks of the PADDED path, and the packed
+        training step declines (`native_train_decline_reason`), as ever.  packed=True keeps the step on the packed path and
+        checkpoints its blocks there (`pooled_cls_train`); batches the packed path declines still run padded and checkpointed.
+        The HF Trainer hands `TrainingArguments.gradient_checkpointing_kwargs` over as ONE keyword of that name: a "packed" entry
+        in it counts as the keyword."""
         self.gradient_checkpointing = True
+        self.checkpoint_packed = bool(packed) or bool((gradient_checkpointing_kwargs or {}).get("packed", False))
 
     def get_input_embeddings(self):
         return self.embeddings.word_embeddings
@@ -957,8 +965,8 @@ class BertEncoder(nn.Module):
             return "shape"
         if getattr(cfg, "hidden_act", "gelu") != "gelu":
             return "activation"
-        if self.gradient_checkpointing:
-            return "gradient checkpointing"    # the padded path keeps that feature
+        if self.gradient_checkpointing and not self.checkpoint_packed:
+            return "gradient checkpointing"    # the bare flag: the padded path keeps that feature (packed=True opts in)
         return None
 
     def pooled_cls_train(self, input_ids, attention_mask, token_type_ids=None):
@@ -967,7 +975,12 @@ class BertEncoder(nn.Module):
         autograd.  The last block computes K / V for every token and everything else for the N CLS rows, so in backward only its
         K / V carry gradient to the non-CLS tokens.  In train mode the attention-probability dropout runs inside the attention
         kernels (seed: one int64 per call from torch's CPU default generator, kept as `last_dropout_seed`; block i uses
-        `ops.bert_layer_seed(seed, i)`) and the hidden dropout sites go through `_hidden_dropout`.  Returns [N, d] or None to
+        `ops.bert_layer_seed(seed, i)`) and the hidden dropout sites go through `_hidden_dropout`.
+        BERT_FUSED_HIDDEN_DROPOUT: the hidden dropout sites run inside the embedding / add + LayerNorm kernels instead, as a
+        stateless function of (`ops.bert_hidden_seed(seed)`, site, packed row, column); the seed is then drawn when any attention
+        or hidden p > 0.  After `gradient_checkpointing_enable(packed=True)` (train mode) that is forced on and every block runs
+        as a non-reentrant `torch.utils.checkpoint` of its input [T, d]: the backward recomputes the block, masks included, from
+        the call's seed, without drawing anything.  Returns [N, d] or None to
         decline (`native_train_decline_reason`, a mask / id condition of `pooled_cls`, or a mask that is not right-padded)."""
         if attention_mask is None or self.native_train_decline_reason() is not None:
             return None
@@ -978,25 +991,32 @@ class BertEncoder(nn.Module):
         if pk is None:
             return None
         cfg, emb = self.config, self.embeddings
-        N, T = pk.N, pk.T
         d, nh = cfg.hidden_size, cfg.num_attention_heads
         scale = 1.0 / math.sqrt(d // nh)
         layers = self.encoder.layer
+        ckpt = self.gradient_checkpointing and self.checkpoint_packed and self.training
+        fused = BERT_FUSED_HIDDEN_DROPOUT or ckpt          # a recomputed block must reproduce its masks: the stateless function
         p_attn = [layer.attention.self.dropout.p if self.training else 0.0 for layer in layers]
+        p_hid = lambda mod: mod.p if self.training else 0.0
+        p_any = list(p_attn)
+        if fused:
+            p_any += [p_hid(emb.dropout)] + [p_hid(m) for layer in layers for m in (layer.attention.output.dropout, layer.output.dropout)]
         seed = 0
-        if any(p > 0 for p in p_attn):
+        if any(p > 0 for p in p_any):
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())     # CPU generator: no device sync
-        self.last_dropout_seed = seed if any(p > 0 for p in p_attn) else None     # None: this call ran without attention dropout
+        self.last_dropout_seed = seed if any(p > 0 for p in p_any) else None     # None: this call drew no seed
+        hseed = _ops.bert_hidden_seed(seed)
 
-        def drop(t, mod):
-            return _hidden_dropout(t, mod.p) if self.training and mod.p > 0 else t
-        x = _ops.bert_embed_ln_train(pk.ids, pk.pos, pk.tts, emb.word_embeddings.weight, emb.token_type_embeddings.weight,
-                                     emb.position_embeddings.weight, emb.LayerNorm.weight, emb.LayerNorm.bias, emb.LayerNorm.eps,
-                                     emb.word_embeddings.padding_idx)
-        x = drop(x, emb.dropout)
-        if len(layers) == 0:
-            return x.index_select(0, pk.cls_idx)
-        for i, layer in enumerate(layers):
+        def add_ln(res, y, mod, site):
+            """LayerNorm(res + dropout(y)) of a BertSelfOutput / BertOutput `mod`: the dropout inside the kernels (fused) or through
+            `_hidden_dropout`."""
+            ln, p = mod.LayerNorm, p_hid(mod.dropout)
+            if fused:
+                return _ops.add_layernorm_train(res, y, ln.weight, ln.bias, ln.eps, p, hseed, site)
+            return _ops.add_layernorm_train(res, _hidden_dropout(y, p) if p > 0 else y, ln.weight, ln.bias, ln.eps)
+
+        def block(i, x):
+            layer = layers[i]
             att, so = layer.attention.self, layer.attention.output
             lseed = _ops.bert_layer_seed(seed, i)
             if i < len(layers) - 1:
@@ -1010,17 +1030,37 @@ class BertEncoder(nn.Module):
                 res = x.index_select(0, pk.cls_idx)
                 q = F.linear(res, att.query.weight, att.query.bias)
                 o = _ops.bidir_attn(q, kv, nh, pk.cu_cls, pk.cu, pk.tiles_cls, pk.k_tiles_cls, scale, p_attn[i], lseed)
-            x = _ops.add_layernorm_train(res, drop(F.linear(o, so.dense.weight, so.dense.bias), so.dropout), so.LayerNorm.weight,
-                                         so.LayerNorm.bias, so.LayerNorm.eps)
+            x = add_ln(res, F.linear(o, so.dense.weight, so.dense.bias), so, _ops.bert_hidden_site(i, False))
             h = _ops.gelu(F.linear(x, layer.intermediate.dense.weight, layer.intermediate.dense.bias))
             out = layer.output
-            x = _ops.add_layernorm_train(x, drop(F.linear(h, out.dense.weight, out.dense.bias), out.dropout),
-                                         out.LayerNorm.weight, out.LayerNorm.bias, out.LayerNorm.eps)
+            return add_ln(x, F.linear(h, out.dense.weight, out.dense.bias), out, _ops.bert_hidden_site(i, True))
+
+        p_emb = p_hid(emb.dropout)
+        x = _ops.bert_embed_ln_train(pk.ids, pk.pos, pk.tts, emb.word_embeddings.weight, emb.token_type_embeddings.weight,
+                                     emb.position_embeddings.weight, emb.LayerNorm.weight, emb.LayerNorm.bias, emb.LayerNorm.eps,
+                                     emb.word_embeddings.padding_idx, p_emb if fused else 0.0, hseed)
+        if not fused and p_emb > 0:
+            x = _hidden_dropout(x, p_emb)
+        if len(layers) == 0:
+            return x.index_select(0, pk.cls_idx)
+        for i in range(len(layers)):
+            if ckpt:
+                # every block, the CLS-only last one included: its input [T, d] and the integer work lists survive the forward;
+                # the recomputation draws nothing (seed and pack are the closure's, every dropout is a stateless function)
+                x = checkpoint(functools.partial(block, i), x, use_reentrant=False, preserve_rng_state=False)
+            else:
+                x = block(i, x)
         return x
 
 
 BERT_NATIVE = True       # BertEncoder.pooled_cls runs the packed hand-written forward; False: it declines and the padded PyTorch
 #                          path runs (the A/B arm of tools/bert_encode_bench.py)
+
+
+BERT_FUSED_HIDDEN_DROPOUT = False  # True: BertEncoder.pooled_cls_train takes the hidden dropout (embedding output, the two
+#                                    `dropout(dense(..))` of a block) inside the row kernels as a stateless function of (seed, site,
+#                                    row, column) (bert_ops.hip) instead of `_hidden_dropout`: other masks than torch's generator
+#                                    gives, the same distribution.  gradient_checkpointing_enable(packed=True) forces it on.
 
 
 BERT_NATIVE_TRAIN = True  # BertEncoder.pooled_cls_train runs the packed hand-written training step; False: it declines and the

@@ -1209,6 +1209,38 @@ def bert_layer_seed(seed: int, layer: int) -> int:
     return (int(seed) + int(layer) * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
 
 
+def bert_hidden_seed(seed: int) -> int:
+    """The seed of the hidden-dropout sites (fused into the row kernels) for a call's `seed`: seed + 0xD1B54A32D192ED03 mod 2^64.
+    The offset is no multiple i * 0x9E3779B97F4A7C15 mod 2^64 with i < 4096 (tests/test_hidden_dropout_host.py), so it equals no
+    `bert_layer_seed(seed, i)` of an encoder of fewer than 4096 blocks: attention and hidden dropout never share a Philox key."""
+    return (int(seed) + 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF
+
+
+def bert_hidden_site(block: int = -1, ffn: bool = False) -> int:
+    """Site index of a hidden dropout: 0 = the embedding output (block < 0), 1 + 2 i = after the attention output dense of block
+    i, 2 + 2 i = after its FFN output dense."""
+    return 0 if block < 0 else 1 + 2 * int(block) + int(bool(ffn))
+
+
+def hidden_dropout_scale(p_drop: float) -> float:
+    """1 / (1 - p_drop) as the f32 value the kernels multiply by (the attention dropout's convention); 1.0 when p_drop quantises
+    to no dropout (p_drop < 2^-17)."""
+    if not 0.0 <= p_drop < 1.0:
+        raise ValueError("hidden_dropout_scale: p_drop must lie in [0, 1)")
+    return float(_lib.load().rpo_hidden_dropout_scale(float(p_drop)))
+
+
+def hidden_dropout_mask(row0: int, rows: int, d: int, p_drop: float, seed: int, site: int, device):
+    """The keep mask (uint8 [rows, d], 1 = kept) of the fused hidden dropout for rows row0.. of `site`; `seed` as handed to the
+    kernels (`bert_hidden_seed` of the call's seed).  Tests and diagnostics: the product never calls it."""
+    lib = _lib.load()
+    mask = torch.empty((rows, d), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        check(lib.rpo_hidden_dropout_mask(row0, rows, d, float(p_drop), int(seed), int(site), mask.data_ptr(),
+                                          torch.cuda.current_stream(device).cuda_stream), "rpo_hidden_dropout_mask")
+    return mask
+
+
 def _heads_ok(who, hd, *ts):
     for t in ts:
         if t.stride(2) != 1 or t.stride(1) != hd:
@@ -1323,11 +1355,35 @@ def layernorm_bwd(s, weight, dy, eps):
     return ds, sums[0], sums[1]
 
 
+def layernorm_drop_bwd(s, weight, dy, eps, p_drop, seed, site_in: int = -1, site_out: int = -1):
+    """`layernorm_bwd` with the fused hidden dropout -> (ds, db or None, dgamma, dbeta).  site_in >= 0: dy is dropped (site_in)
+    as it is loaded; site_out >= 0: db = the dropped rounded ds (site_out), the gradient of the addend that was dropped."""
+    lib = _lib.load()
+    rows, d = s.shape
+    dy = dy if dy.stride(1) == 1 and dy.stride(0) % 8 == 0 and dy.data_ptr() % 16 == 0 else dy.contiguous()
+    ds = torch.empty((rows, d), dtype=s.dtype, device=s.device)
+    db = torch.empty((rows, d), dtype=s.dtype, device=s.device) if site_out >= 0 else None
+    if rows == 0:
+        z = torch.zeros((d,), dtype=torch.float32, device=s.device)
+        return ds, db, z, z.clone()
+    nb = lib.rpo_layernorm_bwd_blocks(rows)
+    part = torch.empty((2, nb, d), dtype=torch.float32, device=s.device)
+    with torch.cuda.device(s.device):
+        check(lib.rpo_layernorm_drop_bwd(s.data_ptr(), s.stride(0), weight.data_ptr(), dy.data_ptr(), dy.stride(0), float(eps),
+                                         ds.data_ptr(), d, _p(db), d, part[0].data_ptr(), part[1].data_ptr(), rows, d, _dt(s),
+                                         float(p_drop), int(seed), int(site_in), int(site_out), _stream(s)),
+              "rpo_layernorm_drop_bwd")
+    sums = part.sum(1)
+    return ds, db, sums[0], sums[1]
+
+
 class _AddLayerNorm(torch.autograd.Function):
-    """y = LayerNorm(a + b) * weight + bias (b may be None) with the backward kernel: ds is the gradient of both addends."""
+    """y = LayerNorm(a + b) * weight + bias (b may be None) with the backward kernel: ds is the gradient of both addends.
+    p_drop > 0 (b required): y = LayerNorm(a + dropout(b)) with the hidden dropout of `site` inside the forward and backward
+    kernels (`hidden_dropout_mask`'s function: nothing but s is saved)."""
 
     @staticmethod
-    def forward(ctx, a, b, weight, bias, eps):
+    def forward(ctx, a, b, weight, bias, eps, p_drop=0.0, seed=0, site=0):
         lib = _lib.load()
         rows, d = a.shape
         for t in (a, b):
@@ -1335,10 +1391,18 @@ class _AddLayerNorm(torch.autograd.Function):
                 raise ValueError("add_layernorm_train: rows must be contiguous")
         y = torch.empty((rows, d), dtype=a.dtype, device=a.device)
         s = torch.empty((rows, d), dtype=a.dtype, device=a.device)
+        ctx.drop = (float(p_drop), int(seed), int(site)) if p_drop > 0 else None
         with torch.cuda.device(a.device):
-            check(lib.rpo_add_layernorm_train_fwd(a.data_ptr(), a.stride(0), _p(b), b.stride(0) if b is not None else 0,
-                                                  weight.data_ptr(), bias.data_ptr(), float(eps), y.data_ptr(), d, s.data_ptr(), d,
-                                                  rows, d, _dt(a), _stream(a)), "rpo_add_layernorm_train_fwd")
+            if ctx.drop is None:
+                check(lib.rpo_add_layernorm_train_fwd(a.data_ptr(), a.stride(0), _p(b), b.stride(0) if b is not None else 0,
+                                                      weight.data_ptr(), bias.data_ptr(), float(eps), y.data_ptr(), d, s.data_ptr(),
+                                                      d, rows, d, _dt(a), _stream(a)), "rpo_add_layernorm_train_fwd")
+            else:
+                if b is None:
+                    raise ValueError("add_layernorm_train: p_drop > 0 needs the addend b that is dropped")
+                check(lib.rpo_add_layernorm_drop_fwd(a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), weight.data_ptr(),
+                                                     bias.data_ptr(), float(eps), y.data_ptr(), d, s.data_ptr(), d, rows, d,
+                                                     _dt(a), *ctx.drop, _stream(a)), "rpo_add_layernorm_drop_fwd")
         ctx.save_for_backward(s, weight)
         ctx.eps, ctx.has_b = float(eps), b is not None
         return y
@@ -1346,20 +1410,26 @@ class _AddLayerNorm(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         s, weight = ctx.saved_tensors
-        ds, dg, db = layernorm_bwd(s, weight, dy, ctx.eps)
-        return ds, (ds if ctx.has_b else None), dg.to(weight.dtype), db.to(weight.dtype), None
+        if ctx.drop is None:
+            ds, dg, db = layernorm_bwd(s, weight, dy, ctx.eps)
+            dadd = ds if ctx.has_b else None
+        else:
+            p_drop, seed, site = ctx.drop
+            ds, dadd, dg, db = layernorm_drop_bwd(s, weight, dy, ctx.eps, p_drop, seed, site_out=site)
+        return ds, dadd, dg.to(weight.dtype), db.to(weight.dtype), None, None, None, None
 
 
-def add_layernorm_train(a, b, weight, bias, eps):
-    """Differentiable `add_layernorm` -> a new contiguous [rows, d]."""
-    return _AddLayerNorm.apply(a, b, weight, bias, eps)
+def add_layernorm_train(a, b, weight, bias, eps, p_drop: float = 0.0, seed: int = 0, site: int = 0):
+    """Differentiable `add_layernorm` -> a new contiguous [rows, d].  p_drop > 0: LayerNorm(a + dropout(b)), the dropout of
+    hidden site `site` fused into the kernels (`seed`: `bert_hidden_seed` of the call's seed); p_drop == 0: as before."""
+    return _AddLayerNorm.apply(a, b, weight, bias, eps, p_drop, seed, site)
 
 
 class _BertEmbedLayerNorm(torch.autograd.Function):
     """`bert_embed_ln` with a backward: the LayerNorm backward kernel, then ds scattered into the three tables."""
 
     @staticmethod
-    def forward(ctx, ids, pos, token_types, word, type_emb, pos_emb, weight, bias, eps, padding_idx):
+    def forward(ctx, ids, pos, token_types, word, type_emb, pos_emb, weight, bias, eps, padding_idx, p_drop=0.0, seed=0):
         lib = _lib.load()
         T, d = ids.shape[0], word.shape[1]
         for t in (word, type_emb, pos_emb):
@@ -1367,11 +1437,20 @@ class _BertEmbedLayerNorm(torch.autograd.Function):
                 raise ValueError("bert_embed_ln_train: embedding tables must be contiguous")
         y = torch.empty((T, d), dtype=word.dtype, device=word.device)
         s = torch.empty((T, d), dtype=word.dtype, device=word.device)
+        ctx.drop = (float(p_drop), int(seed), bert_hidden_site()) if p_drop > 0 else None
         with torch.cuda.device(word.device):
-            check(lib.rpo_bert_embed_ln_train_fwd(ids.data_ptr(), _p(token_types), pos.data_ptr(), T, word.data_ptr(),
-                                                  word.shape[0], type_emb.data_ptr(), type_emb.shape[0], pos_emb.data_ptr(),
-                                                  pos_emb.shape[0], weight.data_ptr(), bias.data_ptr(), float(eps), y.data_ptr(),
-                                                  d, s.data_ptr(), d, d, _dt(word), _stream(word)), "rpo_bert_embed_ln_train_fwd")
+            if ctx.drop is None:
+                check(lib.rpo_bert_embed_ln_train_fwd(ids.data_ptr(), _p(token_types), pos.data_ptr(), T, word.data_ptr(),
+                                                      word.shape[0], type_emb.data_ptr(), type_emb.shape[0], pos_emb.data_ptr(),
+                                                      pos_emb.shape[0], weight.data_ptr(), bias.data_ptr(), float(eps),
+                                                      y.data_ptr(), d, s.data_ptr(), d, d, _dt(word), _stream(word)),
+                      "rpo_bert_embed_ln_train_fwd")
+            else:
+                check(lib.rpo_bert_embed_ln_drop_fwd(ids.data_ptr(), _p(token_types), pos.data_ptr(), T, word.data_ptr(),
+                                                     word.shape[0], type_emb.data_ptr(), type_emb.shape[0], pos_emb.data_ptr(),
+                                                     pos_emb.shape[0], weight.data_ptr(), bias.data_ptr(), float(eps),
+                                                     y.data_ptr(), d, s.data_ptr(), d, d, _dt(word), *ctx.drop, _stream(word)),
+                      "rpo_bert_embed_ln_drop_fwd")
         ctx.save_for_backward(s, weight, ids, pos, token_types)
         ctx.eps, ctx.padding_idx = float(eps), padding_idx
         ctx.tables = (word.shape, type_emb.shape, pos_emb.shape)
@@ -1380,7 +1459,11 @@ class _BertEmbedLayerNorm(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         s, weight, ids, pos, token_types = ctx.saved_tensors
-        ds, dg, db = layernorm_bwd(s, weight, dy, ctx.eps)
+        if ctx.drop is None:
+            ds, dg, db = layernorm_bwd(s, weight, dy, ctx.eps)
+        else:
+            p_drop, seed, site = ctx.drop
+            ds, _, dg, db = layernorm_drop_bwd(s, weight, dy, ctx.eps, p_drop, seed, site_in=site)
         # Embedding gradient = plumbing: stock index_add_ of ds into f32 tables.  It is atomic-based (the order of the adds into one
         # row is not fixed), like the padded path's own embedding backward; every other gradient of the native step is deterministic.
         # Cost: one dense f32 [rows, d] table per embedding and call plus its storage-dtype copy (the word table of XLM-R /
@@ -1405,12 +1488,14 @@ class _BertEmbedLayerNorm(torch.autograd.Function):
             dtype_emb = dtype_emb.to(s.dtype)
         if ctx.needs_input_grad[5]:
             dpos = scatter(ctx.tables[2], pos).to(s.dtype)
-        return None, None, None, dword, dtype_emb, dpos, dg.to(weight.dtype), db.to(weight.dtype), None, None
+        return None, None, None, dword, dtype_emb, dpos, dg.to(weight.dtype), db.to(weight.dtype), None, None, None, None
 
 
-def bert_embed_ln_train(ids, pos, token_types, word, type_emb, pos_emb, weight, bias, eps, padding_idx=None):
-    """Differentiable `bert_embed_ln` (gradients to the three tables and the LayerNorm parameters)."""
-    return _BertEmbedLayerNorm.apply(ids, pos, token_types, word, type_emb, pos_emb, weight, bias, eps, padding_idx)
+def bert_embed_ln_train(ids, pos, token_types, word, type_emb, pos_emb, weight, bias, eps, padding_idx=None, p_drop: float = 0.0,
+                        seed: int = 0):
+    """Differentiable `bert_embed_ln` (gradients to the three tables and the LayerNorm parameters).  p_drop > 0: the output is
+    dropped (hidden site 0, `seed`: `bert_hidden_seed` of the call's seed) inside the kernels; p_drop == 0: as before."""
+    return _BertEmbedLayerNorm.apply(ids, pos, token_types, word, type_emb, pos_emb, weight, bias, eps, padding_idx, p_drop, seed)
 
 
 def gelu_out(u):

@@ -1,0 +1,123 @@
+"""CPU side of the fused hidden dropout and of gradient checkpointing on the packed BERT / XLM-R step: the statistics of the keep
+function's numpy restatement (tests/hidden_dropout_util.py; tests/test_gpu_hidden_dropout.py compares the kernels' dump with it bit
+for bit), the seed that keeps hidden and attention dropout apart, and the opt-in's decline logic."""
+import math
+
+import numpy as np
+import torch
+
+import hidden_dropout_util as HU
+from rankpo_amd import encoder as PE
+from rankpo_amd import ops
+
+ROWS, D, P = 512, 1024, 0.1
+N = ROWS * D
+
+
+def _share():
+    return 1.0 - HU.threshold(P) / 65536.0
+
+
+def test_threshold_and_scale():
+    assert HU.threshold(0.1) == 6554 and HU.threshold(0.5) == 32768 and HU.threshold(0.0) == 0
+    for p in (0.1, 0.5, 0.25, 0.0, 1e-7):
+        assert ops.hidden_dropout_scale(p) == HU.scale(p), p        # the library's f32 factor
+    assert ops.hidden_dropout_scale(0.5) == 2.0 and ops.hidden_dropout_scale(0.0) == 1.0
+
+
+def test_kept_share_within_5_sigma():
+    q = _share()
+    tol = 5 * math.sqrt(q * (1 - q) / N)                             # 5 sqrt(0.09 / 524288) = 2.1e-3
+    assert abs(tol - 2.1e-3) < 1e-4
+    for seed in HU.SEEDS:
+        for site in (0, 1, 2, 47):
+            m = HU.hidden_keep(ops.bert_hidden_seed(seed), site, 0, ROWS, D, P)
+            assert m.shape == (ROWS, D) and m.dtype == np.uint8
+            assert abs(m.mean() - q) <= tol, (seed, site, m.mean(), q, tol)
+            # per row and per column (1024 resp. 512 draws each): no row or column is off by 6 sigma
+            assert np.abs(m.mean(1) - q).max() <= 6 * math.sqrt(q * (1 - q) / D)
+            assert np.abs(m.mean(0) - q).max() <= 6 * math.sqrt(q * (1 - q) / ROWS)
+
+
+def test_sites_and_seeds_are_independent():
+    """Two sites, two seeds, and two row windows agree on the product of the shares: P(both kept) = q^2, not more."""
+    q = _share()
+    tol = 5 * math.sqrt(q * q * (1 - q * q) / N)
+    s0, s1 = (ops.bert_hidden_seed(s) for s in HU.SEEDS[:2])
+    base = HU.hidden_keep(s0, 1, 0, ROWS, D, P)
+    for name, other in (("site", HU.hidden_keep(s0, 2, 0, ROWS, D, P)), ("seed", HU.hidden_keep(s1, 1, 0, ROWS, D, P)),
+                        ("seed + 1", HU.hidden_keep(s0 + 1, 1, 0, ROWS, D, P)),
+                        ("rows", HU.hidden_keep(s0, 1, ROWS, ROWS, D, P))):
+        both = (base & other).mean()
+        assert abs(both - q * q) <= tol, (name, both, q * q, tol)
+    # a window of a mask = the same entries of the whole mask
+    assert np.array_equal(HU.hidden_keep(s0, 1, 5, 3, D, P), base[5:8])
+
+
+def test_hidden_seed_never_equals_a_layer_seed():
+    for seed in (0, 1, 12345, 2 ** 31, 2 ** 63 - 2, 0x9E3779B97F4A7C15, 0xD1B54A32D192ED03, 2 ** 64 - 1) + HU.SEEDS:
+        h = ops.bert_hidden_seed(seed)
+        assert 0 <= h < 2 ** 64
+        assert h not in {ops.bert_layer_seed(seed, i) for i in range(4096)}
+    assert [ops.bert_hidden_site(), ops.bert_hidden_site(0), ops.bert_hidden_site(0, True), ops.bert_hidden_site(3),
+            ops.bert_hidden_site(3, True)] == [0, 1, 2, 7, 8]
+
+
+def _bert():
+    return PE.BertEncoder(PE.bert_config(vocab_size=64, hidden_size=64, intermediate_size=128, num_hidden_layers=1,
+                                         num_attention_heads=2, max_position_embeddings=32, hidden_dropout_prob=0.1,
+                                         attention_probs_dropout_prob=0.1))
+
+
+def test_packed_checkpointing_opt_in_does_not_decline(monkeypatch):
+    monkeypatch.setattr(PE, "_on_hip_device", lambda t: True)
+    assert PE.BERT_FUSED_HIDDEN_DROPOUT is False
+    enc = _bert().half().train()
+    assert enc.gradient_checkpointing is False and enc.checkpoint_packed is False
+    enc.gradient_checkpointing_enable()
+    assert enc.gradient_checkpointing and not enc.checkpoint_packed
+    assert enc.native_train_decline_reason() == "gradient checkpointing"       # the bare call: as ever
+    enc.gradient_checkpointing_enable(packed=True)
+    assert enc.gradient_checkpointing and enc.checkpoint_packed
+    assert enc.native_train_decline_reason() is None
+    enc.gradient_checkpointing_enable(use_reentrant=False)                      # HF-style keywords: still the bare call
+    assert enc.native_train_decline_reason() == "gradient checkpointing"
+    enc.gradient_checkpointing_enable(gradient_checkpointing_kwargs={"use_reentrant": False})
+    assert enc.native_train_decline_reason() == "gradient checkpointing"
+    enc.gradient_checkpointing_enable(gradient_checkpointing_kwargs={"packed": True})     # how the HF Trainer passes its kwargs
+    assert enc.checkpoint_packed and enc.native_train_decline_reason() is None
+    # the other conditions still decline under the opt-in
+    enc.gradient_checkpointing_enable(packed=True)
+    with torch.no_grad():
+        assert enc.native_train_decline_reason() == "grad disabled"
+    assert _bert().train().native_train_decline_reason() == "storage dtype"
+
+
+def test_model_for_training_forwards_the_keyword(monkeypatch):
+    import rankpo_amd
+    monkeypatch.setattr(PE, "_on_hip_device", lambda t: True)
+    model = rankpo_amd.ModelForTraining(encoder=_bert().half(), temperature=0.02).train()
+    model.gradient_checkpointing_enable()
+    assert model.model.native_train_decline_reason() == "gradient checkpointing"
+    model.gradient_checkpointing_enable(packed=True)
+    assert model.model.checkpoint_packed and model.model.native_train_decline_reason() is None
+
+
+def test_new_entry_points_are_bound():
+    from rankpo_amd import _lib
+    for name in ("rpo_add_layernorm_drop_fwd", "rpo_bert_embed_ln_drop_fwd", "rpo_layernorm_drop_bwd", "rpo_hidden_dropout_mask",
+                 "rpo_hidden_dropout_scale"):
+        assert name in _lib.SIGNATURES
+    lib = _lib.load()
+    assert lib.rpo_hidden_dropout_scale(1.0) == 0.0 and lib.rpo_hidden_dropout_scale(-0.5) == 0.0   # outside [0, 1)
+    # rows == 0 is a no-op success and bad arguments are status codes: every call below returns before a launch, so the
+    # non-null, 16-byte aligned dummy pointer is never dereferenced
+    p = 16
+    assert lib.rpo_add_layernorm_drop_fwd(p, 64, p, 64, p, p, 1e-5, p, 64, p, 64, 0, 64, 2, 0.1, 5, 1, None) == 0
+    assert lib.rpo_layernorm_drop_bwd(p, 64, p, p, 64, 1e-5, p, 64, p, 64, p, p, 0, 64, 2, 0.1, 5, -1, 1, None) == 0
+    assert lib.rpo_hidden_dropout_mask(0, 0, 64, 0.1, 5, 0, p, None) == 0
+    assert lib.rpo_add_layernorm_drop_fwd(p, 64, p, 64, p, p, 1e-5, p, 64, p, 64, 0, 64, 2, 1.0, 5, 1, None) == -1    # p_drop
+    assert lib.rpo_add_layernorm_drop_fwd(p, 64, p, 64, p, p, 1e-5, p, 64, p, 64, 0, 64, 0, 0.1, 5, 1, None) == -2    # f32
+    assert lib.rpo_add_layernorm_drop_fwd(p, 12, p, 12, p, p, 1e-5, p, 12, p, 12, 0, 12, 2, 0.1, 5, 1, None) == -2    # d % 8
+    assert lib.rpo_add_layernorm_drop_fwd(p, 64, p, 64, p, p, 1e-5, p, 64, p, 64, 0, 64, 2, 0.1, 5, -1, None) == -1   # site
+    assert lib.rpo_layernorm_drop_bwd(p, 8192, p, p, 8192, 1e-5, p, 8192, p, 8192, p, p, 0, 8192, 2, 0.1, 5, -1, 1, None) == -2   # d > 4096
