@@ -418,6 +418,35 @@ int rpo_bert_embed_ln_fwd(const int* ids, const int* token_types, const int* pos
                           rpo_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * (9b) f32 storage: the forward of section (9) for an encoder kept in float32 (opt-in: encoder.BERT_NATIVE_F32 /
+ * BertEncoder.native_f32, ModelForInference(packed_f32=True)).  Entry points of their own: the entries of (9) keep answering
+ * RPO_DT_F32 with RPO_ERR_UNSUPPORTED.  Argument lists of the 16-bit siblings without `dtype`; strides in elements (floats);
+ * shapes, work lists, CLS-only mode, status codes as in (9).  No allocation, no host sync, no atomics.  Forward only: the
+ * training entries of (10) have no f32 form.
+ *
+ * rpo_bidir_attn_fwd_f32: the attention of rpo_bidir_attn_fwd on v_mfma_f32_16x16x4_f32: f32 operands, exact f32 products,
+ * f32 accumulation; P stays f32 and is never rounded to 16 bits.  The exponent is taken of ((s - m) |scale|) log2(e) with m the
+ * running maximum of the raw scores, so no rounding happens at the magnitude of a large score.  lse (may be NULL): f32
+ * [num_heads][total_q], natural log.  head_dim 32 or 64, num_heads == num_kv_heads, tile_cols == 2, q_block == 32 (anything
+ * else: RPO_ERR_UNSUPPORTED); q / k / v / out 16-byte aligned with strides % 4 == 0.  Every sequence length >= 1 works.
+ *
+ * rpo_add_layernorm_fwd_f32 / rpo_gelu_fwd_f32 / rpo_bert_embed_ln_fwd_f32: the row kernels of (9) instantiated for float (4
+ * elements per 16-byte vector).  a + b and (word + type) + pos are plain f32 adds (nothing to round); two-pass mean / centred
+ * variance.  d (cols) % 8 == 0, d <= 4096, 16-byte aligned, strides % 4 == 0.
+ * --------------------------------------------------------------------------------------------- */
+int rpo_bidir_attn_fwd_f32(const void* q, const void* k, const void* v, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                           const int* cu_seqlens_q, const int* cu_seqlens_k, const int* tiles, int64_t ntiles,
+                           int64_t tile_cols, int64_t q_block, int64_t total_q, int64_t num_heads, int64_t num_kv_heads,
+                           int64_t head_dim, float scale, void* out, int64_t out_stride, float* lse, rpo_stream_t stream);
+int rpo_add_layernorm_fwd_f32(const void* a, int64_t lda, const void* b, int64_t ldb, const void* gamma, const void* beta,
+                              float eps, void* y, int64_t ldy, int64_t rows, int64_t d, rpo_stream_t stream);
+int rpo_gelu_fwd_f32(void* x, int64_t rows, int64_t cols, int64_t ld, rpo_stream_t stream);
+int rpo_bert_embed_ln_fwd_f32(const int* ids, const int* token_types, const int* pos, int64_t tokens, const void* word,
+                              int64_t vocab, const void* type_emb, int64_t n_types, const void* pos_emb, int64_t n_pos,
+                              const void* gamma, const void* beta, float eps, void* y, int64_t ldy, int64_t d,
+                              rpo_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * (10) packed TRAINING step of the BERT / XLM-R block (rankpo_amd/csrc/bert_ops.hip; BertEncoder.pooled_cls_train, used by
  * ModelForTraining.embed for CLS-pooled models).  bf16 or fp16 storage (RPO_DT_F32 is RPO_ERR_UNSUPPORTED), f32 arithmetic,
  * no allocation, no host sync, no atomics: deterministic.  Shapes, strides, work lists and alignment as in section (9) unless

@@ -6,6 +6,9 @@
 //   rpo_add_layernorm_fwd  LayerNorm(a + b) (HF BertSelfOutput / BertOutput: `LayerNorm(dropout(dense(h)) + input)`)
 //   rpo_gelu_fwd           exact erf GELU in place (HF BertIntermediate with hidden_act "gelu")
 //   rpo_bert_embed_ln_fwd  word + token type + position embedding gather, then LayerNorm (HF BertEmbeddings.forward)
+// the same four on f32 storage, as entries of their own (header section 9b; the four above answer RPO_DT_F32 with UNSUPPORTED):
+//   rpo_bidir_attn_fwd_f32       the attention on the f32-input MFMA (v_mfma_f32_16x16x4_f32), P never rounded
+//   rpo_add_layernorm_fwd_f32 / rpo_gelu_fwd_f32 / rpo_bert_embed_ln_fwd_f32   the row kernels instantiated for float
 // and the TRAINING step on the same packed layout (`BertEncoder.pooled_cls_train`):
 //   rpo_bidir_attn_train_fwd     the forward with attention-probability dropout (a template arm of the same kernel)
 //   rpo_bidir_attn_bwd           dQ kernel + dK/dV kernel in the forward's wave layout, P recomputed from lse, dropout replayed
@@ -252,6 +255,160 @@ __global__ __launch_bounds__(64) void bidir_attn_fwd_kernel(
             *reinterpret_cast<uint2_t*>(op + 16 * b) = pk;
         }
         if (lse && g == 0) lse[(int64_t)h * total_q + tq0 + qi] = L > 0.f ? (m[s] + log2f(L)) * kLn2 : -INFINITY;
+    }
+}
+
+// ---- (1a) the same attention on f32 storage (rpo_bidir_attn_fwd_f32) ---------------------------------
+// The wave layout, the work list and the accumulator map of the kernel above, on v_mfma_f32_16x16x4_f32 (f32 operands, exact f32
+// products, f32 accumulation: nothing is rounded to 16 bits anywhere).  Operands are ONE f32 per lane: A[row l & 15][k = l >> 4],
+// B[k = l >> 4][col l & 15].
+//   S^T = K Q^T: a lane keeps the HD / 4 consecutive head dims HD / 4 g .. of its key row (A) and of its query row (B), loaded as
+//   16-byte vectors; MFMA t of the HD / 4 takes element t of both, so its k slot g is head dim HD / 4 g + t (any one-to-one map
+//   of k slots to head dims gives the same dot product, as long as A and B use the same one).
+//   O^T = V^T P^T: MFMA t of a 16-key half takes p[t] as B as it lies in the accumulator (k slot g = key 4 g + t) and
+//   A = V[key 4 g + t][16 b + r] from the LDS tile.  Row stride HD + 4 words: the two lane groups of a ds_read_b32 half
+//   (g, g + 1: 4 rows apart) then read banks 16 apart, and rows stay 16-byte aligned for the staging stores.
+// One 16x16x4 MFMA issues in 32 cycles and its result is ready after 40: consecutive MFMAs go round four accumulators (scores:
+// two query tiles x two chains) or the two query tiles and the HD / 16 output blocks (PV), never the same one back to back.
+// The exponent is exp2(((s - m) |scale|) log2 e) with m the running maximum of the RAW scores (sign-adjusted by negating Q when
+// scale < 0) and log2 e carried as hi + lo: the roundings are relative to the DISTANCE from the maximum, none is taken at the
+// magnitude of a large score.
+constexpr float kLog2eHi = 1.44269502162933349609375f;        // (float)log2(e)
+constexpr float kLog2eLo = 1.92596299112661746e-8f;           // log2(e) - kLog2eHi
+template <int HD>
+__global__ __launch_bounds__(64) void bidir_attn_fwd_f32_kernel(
+    const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, int64_t q_stride, int64_t k_stride,
+    int64_t v_stride, const int* __restrict__ cu_q, const int* __restrict__ cu_k, const int* __restrict__ tiles,
+    float scale_abs, float sgn, float* __restrict__ out, int64_t out_stride, float* __restrict__ lse, int64_t total_q) {
+    constexpr int QS = kAttnQBlock / 16;   // query tiles per wave
+    constexpr int DK = HD / 4;             // MFMAs of a 16x16 score block = head dims per lane
+    constexpr int OB = HD / 16;            // 16-row blocks of O^T
+    constexpr int VLD = HD + 4;            // LDS row stride (words)
+    constexpr int VCH = kAttnKeys * HD / 4 / 64;   // 16-byte V chunks per lane per step
+    __shared__ __attribute__((aligned(16))) float vs[kAttnKeys * VLD];
+
+    const int entry = blockIdx.x, h = blockIdx.y;
+    const int seq = tiles[2 * entry], q0 = tiles[2 * entry + 1];
+    const int tq0 = cu_q[seq], lq = cu_q[seq + 1] - tq0;
+    const int tk0 = cu_k[seq], lk = cu_k[seq + 1] - tk0;
+    const int lane = threadIdx.x, r = lane & 15, g = lane >> 4;
+    const int64_t hcol = (int64_t)h * HD;
+    if (lq <= 0) return;
+
+    float qf[QS][DK];
+#pragma unroll
+    for (int s = 0; s < QS; ++s) {
+        const int qi = min(q0 + s * 16 + r, lq - 1);     // rows past the end: loaded (in bounds), never stored
+        const float* qp = q + (int64_t)(tq0 + qi) * q_stride + hcol + DK * g;
+#pragma unroll
+        for (int j = 0; j < DK / 4; ++j) {
+            const float4_t t = *reinterpret_cast<const float4_t*>(qp + 4 * j);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) qf[s][4 * j + e] = t[e] * sgn;
+        }
+    }
+    float m[QS], l[QS];
+    float4_t o[QS][OB];
+#pragma unroll
+    for (int s = 0; s < QS; ++s) {
+        m[s] = -INFINITY;
+        l[s] = 0.f;
+#pragma unroll
+        for (int b = 0; b < OB; ++b) o[s][b] = float4_t{0.f, 0.f, 0.f, 0.f};
+    }
+
+    for (int kt = 0; kt < lk; kt += kAttnKeys) {
+        // V rows of this step -> registers (clamped to the sequence: in bounds; masked keys get p = 0)
+        float4_t vr[VCH];
+#pragma unroll
+        for (int c = 0; c < VCH; ++c) {
+            const int idx = lane + 64 * c, key = idx / (HD / 4), c4 = idx - key * (HD / 4);
+            const int kk = min(kt + key, lk - 1);
+            vr[c] = *reinterpret_cast<const float4_t*>(v + (int64_t)(tk0 + kk) * v_stride + hcol + 4 * c4);
+        }
+        float4_t sc[2][QS];
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int kk = min(kt + b * 16 + r, lk - 1);
+            const float* kp = k + (int64_t)(tk0 + kk) * k_stride + hcol + DK * g;
+            float4_t kf[DK / 4];
+#pragma unroll
+            for (int j = 0; j < DK / 4; ++j) kf[j] = *reinterpret_cast<const float4_t*>(kp + 4 * j);
+            // two chains per score block (even / odd t), added at the end: half the length of each rounding chain, and four
+            // independent accumulators in flight
+            float4_t odd[QS];
+#pragma unroll
+            for (int s = 0; s < QS; ++s) sc[b][s] = odd[s] = float4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int t = 0; t < DK; t += 2)
+#pragma unroll
+                for (int s = 0; s < QS; ++s) {
+                    sc[b][s] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[t / 4][t % 4], qf[s][t], sc[b][s], 0, 0, 0);
+                    odd[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[t / 4][t % 4 + 1], qf[s][t + 1], odd[s], 0, 0, 0);
+                }
+#pragma unroll
+            for (int s = 0; s < QS; ++s) sc[b][s] += odd[s];
+        }
+        __syncthreads();                                   // the previous step's V reads are done
+#pragma unroll
+        for (int c = 0; c < VCH; ++c) {
+            const int idx = lane + 64 * c, key = idx / (HD / 4), c4 = idx - key * (HD / 4);
+            *reinterpret_cast<float4_t*>(&vs[key * VLD + 4 * c4]) = vr[c];
+        }
+        // online softmax; sc[b][s][i] = raw score of key kt + 16 b + 4 g + i, query q0 + 16 s + r; afterwards the probability
+#pragma unroll
+        for (int s = 0; s < QS; ++s) {
+            float mx = -INFINITY;
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (kt + b * 16 + 4 * g + i < lk) mx = fmaxf(mx, sc[b][s][i]);
+            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            const float mn = fmaxf(m[s], mx);              // finite: key kt is always valid
+            const float da = (m[s] - mn) * scale_abs;
+            const float alpha = m[s] == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(fmaf(da, kLog2eHi, da * kLog2eLo));
+            m[s] = mn;
+            float ps = 0.f;
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float dx = (sc[b][s][i] - mn) * scale_abs;
+                    const float p = (kt + b * 16 + 4 * g + i < lk) ? __builtin_amdgcn_exp2f(fmaf(dx, kLog2eHi, dx * kLog2eLo)) : 0.f;
+                    sc[b][s][i] = p;
+                    ps += p;
+                }
+            l[s] = fmaf(l[s], alpha, ps);                  // per-lane partial sum: alpha is the same on the 4 lanes of a query
+#pragma unroll
+            for (int b = 0; b < OB; ++b) o[s][b] *= alpha;
+        }
+        __syncthreads();                                   // V tile visible
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int ob = 0; ob < OB; ++ob) {
+                    const float va = vs[(16 * b + 4 * g + t) * VLD + 16 * ob + r];
+#pragma unroll
+                    for (int s = 0; s < QS; ++s) o[s][ob] = __builtin_amdgcn_mfma_f32_16x16x4f32(va, sc[b][s][t], o[s][ob], 0, 0, 0);
+                }
+    }
+
+#pragma unroll
+    for (int s = 0; s < QS; ++s) {
+        float L = l[s];
+        L += __shfl_xor(L, 16, 64);
+        L += __shfl_xor(L, 32, 64);
+        const int qi = q0 + s * 16 + r;
+        if (qi >= lq) continue;
+        const float inv = L > 0.f ? 1.0f / L : 0.f;
+        float* op = out + (int64_t)(tq0 + qi) * out_stride + hcol + 4 * g;
+#pragma unroll
+        for (int b = 0; b < OB; ++b) *reinterpret_cast<float4_t*>(op + 16 * b) = o[s][b] * inv;
+        if (lse && g == 0) lse[(int64_t)h * total_q + tq0 + qi] = L > 0.f ? fmaf(m[s], scale_abs, logf(L)) : -INFINITY;
     }
 }
 
@@ -599,36 +756,38 @@ __global__ __launch_bounds__(256) void dropout_mask_kernel(int q_row0, int k_row
 // ---- (2)-(4) row kernels: one wave per row, NV 16-byte vectors per lane ------------------------------
 constexpr int kRowThreads = 256;
 
-// y = (x - mean) rstd gamma + beta over a row held in registers (columns 8 (lane + 64 j) .. + 7), statistics in f32, rounded once
+// y = (x - mean) rstd gamma + beta over a row held in registers (columns V (lane + 64 j) .. + V - 1, V = Elem<T>::kVec = elements
+// per 16 bytes: 8, or 4 for f32 storage), statistics in f32, rounded once
 template <typename T, int NV>
 __device__ __forceinline__ void layernorm_store(Vec16<T> (&x)[NV], const T* __restrict__ gamma, const T* __restrict__ beta,
                                                 float eps, T* __restrict__ y, int d, int lane) {
+    constexpr int V = Elem<T>::kVec;
     float sum = 0.f;
 #pragma unroll
     for (int j = 0; j < NV; ++j)
-        if (8 * (lane + 64 * j) < d)
+        if (V * (lane + 64 * j) < d)
 #pragma unroll
-            for (int e = 0; e < 8; ++e) sum += x[j].v[e];
+            for (int e = 0; e < V; ++e) sum += x[j].v[e];
     const float mean = wave_sum(sum) / (float)d;
     float sq = 0.f;
 #pragma unroll
     for (int j = 0; j < NV; ++j)
-        if (8 * (lane + 64 * j) < d)
+        if (V * (lane + 64 * j) < d)
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
+            for (int e = 0; e < V; ++e) {
                 const float c = x[j].v[e] - mean;
                 sq = fmaf(c, c, sq);
             }
     const float rstd = rsqrtf(wave_sum(sq) / (float)d + eps);
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
-        const int c0 = 8 * (lane + 64 * j);
+        const int c0 = V * (lane + 64 * j);
         if (c0 < d) {
             Vec16<T> gw, bw;
             gw.load(gamma + c0);
             bw.load(beta + c0);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) x[j].v[e] = fmaf((x[j].v[e] - mean) * rstd, gw.v[e], bw.v[e]);
+            for (int e = 0; e < V; ++e) x[j].v[e] = fmaf((x[j].v[e] - mean) * rstd, gw.v[e], bw.v[e]);
             x[j].store(y + c0);
         }
     }
@@ -641,19 +800,20 @@ __global__ __launch_bounds__(kRowThreads) void add_layernorm_kernel(const T* __r
                                                                      int64_t ldy, T* __restrict__ s_out, int64_t lds,
                                                                      int64_t rows, int d) {
     const int64_t row = (int64_t)blockIdx.x * (kRowThreads / 64) + (threadIdx.x >> 6);
+    constexpr int V = Elem<T>::kVec;
     const int lane = threadIdx.x & 63;
     if (row >= rows) return;
     Vec16<T> x[NV];
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
-        const int c0 = 8 * (lane + 64 * j);
+        const int c0 = V * (lane + 64 * j);
         if (c0 < d) {
             x[j].load(a + row * lda + c0);
             if (b) {
                 Vec16<T> t;
                 t.load(b + row * ldb + c0);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) x[j].v[e] = Elem<T>::round(x[j].v[e] + t.v[e]);   // the reference's rounded sum
+                for (int e = 0; e < V; ++e) x[j].v[e] = Elem<T>::round(x[j].v[e] + t.v[e]);   // the reference's rounded sum
             }
             if (s_out) x[j].store(s_out + row * lds + c0);   // training: the backward recomputes the statistics from it
         }
@@ -668,6 +828,7 @@ __global__ __launch_bounds__(kRowThreads) void bert_embed_ln_kernel(
     int64_t npos, const T* __restrict__ gamma, const T* __restrict__ beta, float eps, T* __restrict__ y, int64_t ldy, T* __restrict__ s_out,
     int64_t lds, int d) {
     const int64_t row = (int64_t)blockIdx.x * (kRowThreads / 64) + (threadIdx.x >> 6);
+    constexpr int V = Elem<T>::kVec;
     const int lane = threadIdx.x & 63;
     if (row >= tokens) return;
     // indices are clamped into their tables: an id out of range reads a valid row, never foreign memory (the Python wrapper
@@ -678,14 +839,14 @@ __global__ __launch_bounds__(kRowThreads) void bert_embed_ln_kernel(
     Vec16<T> x[NV];
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
-        const int c0 = 8 * (lane + 64 * j);
+        const int c0 = V * (lane + 64 * j);
         if (c0 < d) {
             Vec16<T> t, p;
             x[j].load(word + wi * d + c0);
             t.load(temb + ti * d + c0);
             p.load(pemb + pi * d + c0);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) x[j].v[e] = Elem<T>::round(Elem<T>::round(x[j].v[e] + t.v[e]) + p.v[e]);   // (w + t) + p
+            for (int e = 0; e < V; ++e) x[j].v[e] = Elem<T>::round(Elem<T>::round(x[j].v[e] + t.v[e]) + p.v[e]);   // (w + t) + p
             if (s_out) x[j].store(s_out + row * lds + c0);
         }
     }
@@ -694,14 +855,15 @@ __global__ __launch_bounds__(kRowThreads) void bert_embed_ln_kernel(
 
 template <typename T>
 __global__ __launch_bounds__(256) void gelu_kernel(T* __restrict__ x, int64_t rows, int64_t cols, int64_t ld) {
-    const int64_t vpr = cols / 8, n = rows * vpr;
+    constexpr int V = Elem<T>::kVec;
+    const int64_t vpr = cols / V, n = rows * vpr;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t rr = i / vpr, c = (i - rr * vpr) * 8;
+        const int64_t rr = i / vpr, c = (i - rr * vpr) * V;
         T* p = x + rr * ld + c;
         Vec16<T> t;
         t.load(p);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) t.v[e] = 0.5f * t.v[e] * (1.0f + erff(t.v[e] * 0.70710678118654752f));
+        for (int e = 0; e < V; ++e) t.v[e] = 0.5f * t.v[e] * (1.0f + erff(t.v[e] * 0.70710678118654752f));
         t.store(p);
     }
 }
@@ -948,6 +1110,96 @@ extern "C" int rpo_bert_embed_ln_fwd(const int* ids, const int* token_types, con
         RPO_ROW_DISPATCH(bert_embed_ln_kernel, f16_t, nv, grid, st, ids, token_types, pos, tokens, (const f16_t*)word, vocab,
                          (const f16_t*)type_emb, n_types, (const f16_t*)pos_emb, n_pos, (const f16_t*)gamma,
                          (const f16_t*)beta, eps, (f16_t*)y, ldy, (f16_t*)nullptr, (int64_t)0, (int)d);
+    return rpo_launch_status();
+}
+
+// ---- f32 storage (header section 9b): entries of their own; the ones above keep answering RPO_DT_F32 with UNSUPPORTED --------
+namespace {
+int row_vectors_f32(int64_t d) {            // NV of the row kernels on 4-element vectors: 1 .. 16 (d <= 4096); 0 = too wide
+    const int64_t nv = rpo_cdiv(d, 256);
+    return nv <= 1 ? 1 : nv <= 2 ? 2 : nv <= 4 ? 4 : nv <= 8 ? 8 : nv <= 16 ? 16 : 0;
+}
+}  // namespace
+
+#define RPO_ROW_DISPATCH_F32(KERNEL, NV, GRID, ST, ...)                                                      \
+    do {                                                                                                     \
+        if (NV == 16) RPO_LAUNCH((KERNEL<float, 16>), GRID, dim3(kRowThreads), 0, ST, __VA_ARGS__);          \
+        else RPO_ROW_DISPATCH(KERNEL, float, NV, GRID, ST, __VA_ARGS__);                                     \
+    } while (0)
+
+extern "C" int rpo_bidir_attn_fwd_f32(const void* q, const void* k, const void* v, int64_t q_stride, int64_t k_stride,
+                                      int64_t v_stride, const int* cu_seqlens_q, const int* cu_seqlens_k, const int* tiles,
+                                      int64_t ntiles, int64_t tile_cols, int64_t q_block, int64_t total_q, int64_t num_heads,
+                                      int64_t num_kv_heads, int64_t head_dim, float scale, void* out, int64_t out_stride,
+                                      float* lse, rpo_stream_t stream) {
+    if (!q || !k || !v || !cu_seqlens_q || !cu_seqlens_k || !tiles || !out || ntiles < 0 || total_q <= 0 || num_heads <= 0 ||
+        num_kv_heads <= 0 || head_dim <= 0 || q_stride <= 0 || k_stride <= 0 || v_stride <= 0 || out_stride <= 0 ||
+        !(fabsf(scale) <= 3.0e38f))
+        return RPO_ERR_INVALID_ARG;
+    if ((head_dim != 32 && head_dim != 64) || num_heads != num_kv_heads || tile_cols != 2 || q_block != kAttnQBlock ||
+        ntiles > 0x7fffffff || num_heads > 65535)
+        return RPO_ERR_UNSUPPORTED;
+    if (!rpo_aligned16(q) || !rpo_aligned16(k) || !rpo_aligned16(v) || !rpo_aligned16(out) || q_stride % 4 || k_stride % 4 ||
+        v_stride % 4 || out_stride % 4)
+        return RPO_ERR_UNSUPPORTED;
+    if (ntiles == 0) return RPO_OK;
+    const dim3 grid((unsigned)ntiles, (unsigned)num_heads), block(64);
+    hipStream_t st = (hipStream_t)stream;
+    const float sa = fabsf(scale), sgn = scale < 0.f ? -1.0f : 1.0f;
+    if (head_dim == 32)
+        RPO_LAUNCH(bidir_attn_fwd_f32_kernel<32>, grid, block, 0, st, (const float*)q, (const float*)k, (const float*)v, q_stride,
+                   k_stride, v_stride, cu_seqlens_q, cu_seqlens_k, tiles, sa, sgn, (float*)out, out_stride, lse, total_q);
+    else
+        RPO_LAUNCH(bidir_attn_fwd_f32_kernel<64>, grid, block, 0, st, (const float*)q, (const float*)k, (const float*)v, q_stride,
+                   k_stride, v_stride, cu_seqlens_q, cu_seqlens_k, tiles, sa, sgn, (float*)out, out_stride, lse, total_q);
+    return rpo_launch_status();
+}
+
+extern "C" int rpo_add_layernorm_fwd_f32(const void* a, int64_t lda, const void* b, int64_t ldb, const void* gamma,
+                                         const void* beta, float eps, void* y, int64_t ldy, int64_t rows, int64_t d,
+                                         rpo_stream_t stream) {
+    if (!a || !gamma || !beta || !y || rows < 0 || d <= 0 || lda < d || ldy < d || (b && ldb < d)) return RPO_ERR_INVALID_ARG;
+    const int nv = row_vectors_f32(d);
+    if (d % 8 || nv == 0) return RPO_ERR_UNSUPPORTED;
+    if (!rpo_aligned16(a) || (b && !rpo_aligned16(b)) || !rpo_aligned16(gamma) || !rpo_aligned16(beta) || !rpo_aligned16(y) ||
+        lda % 4 || (b && ldb % 4) || ldy % 4)
+        return RPO_ERR_UNSUPPORTED;
+    if (rows == 0) return RPO_OK;
+    const dim3 grid((unsigned)rpo_cdiv(rows, kRowThreads / 64));
+    hipStream_t st = (hipStream_t)stream;
+    RPO_ROW_DISPATCH_F32(add_layernorm_kernel, nv, grid, st, (const float*)a, lda, (const float*)b, ldb, (const float*)gamma,
+                         (const float*)beta, eps, (float*)y, ldy, (float*)nullptr, (int64_t)0, rows, (int)d);
+    return rpo_launch_status();
+}
+
+extern "C" int rpo_gelu_fwd_f32(void* x, int64_t rows, int64_t cols, int64_t ld, rpo_stream_t stream) {
+    if (!x || rows < 0 || cols <= 0 || ld < cols) return RPO_ERR_INVALID_ARG;
+    if (cols % 8 || ld % 4 || !rpo_aligned16(x)) return RPO_ERR_UNSUPPORTED;
+    if (rows == 0) return RPO_OK;
+    const int64_t n = rows * (cols / 4), nb = rpo_cdiv(n, 256);
+    const dim3 grid((unsigned)(nb < 8192 ? nb : 8192)), block(256);
+    RPO_LAUNCH(gelu_kernel<float>, grid, block, 0, (hipStream_t)stream, (float*)x, rows, cols, ld);
+    return rpo_launch_status();
+}
+
+extern "C" int rpo_bert_embed_ln_fwd_f32(const int* ids, const int* token_types, const int* pos, int64_t tokens, const void* word,
+                                         int64_t vocab, const void* type_emb, int64_t n_types, const void* pos_emb, int64_t n_pos,
+                                         const void* gamma, const void* beta, float eps, void* y, int64_t ldy, int64_t d,
+                                         rpo_stream_t stream) {
+    if (!ids || !pos || !word || !type_emb || !pos_emb || !gamma || !beta || !y || tokens < 0 || vocab <= 0 || n_types <= 0 ||
+        n_pos <= 0 || d <= 0 || ldy < d)
+        return RPO_ERR_INVALID_ARG;
+    const int nv = row_vectors_f32(d);
+    if (d % 8 || nv == 0 || ldy % 4) return RPO_ERR_UNSUPPORTED;
+    if (!rpo_aligned16(word) || !rpo_aligned16(type_emb) || !rpo_aligned16(pos_emb) || !rpo_aligned16(gamma) ||
+        !rpo_aligned16(beta) || !rpo_aligned16(y))
+        return RPO_ERR_UNSUPPORTED;
+    if (tokens == 0) return RPO_OK;
+    const dim3 grid((unsigned)rpo_cdiv(tokens, kRowThreads / 64));
+    hipStream_t st = (hipStream_t)stream;
+    RPO_ROW_DISPATCH_F32(bert_embed_ln_kernel, nv, grid, st, ids, token_types, pos, tokens, (const float*)word, vocab,
+                         (const float*)type_emb, n_types, (const float*)pos_emb, n_pos, (const float*)gamma, (const float*)beta, eps,
+                         (float*)y, ldy, (float*)nullptr, (int64_t)0, (int)d);
     return rpo_launch_status();
 }
 

@@ -798,6 +798,7 @@ class BertEncoder(nn.Module):
         self.gradient_checkpointing = False
         self.checkpoint_packed = False         # gradient_checkpointing_enable(packed=True): checkpoint the blocks of the packed step
         self.last_dropout_seed = None          # dropout seed of the latest `pooled_cls_train` call (tests read it)
+        self.native_f32 = False                # True: `pooled_cls` also takes float32 storage (as BERT_NATIVE_F32, for this model)
         self.apply(self._init)
 
     def _init(self, m):
@@ -852,7 +853,8 @@ class BertEncoder(nn.Module):
             return "training with dropout"     # dropout is not in the kernels (training is a later step)
         if not _on_hip_device(w):
             return "not on a HIP device"
-        if w.dtype not in (torch.bfloat16, torch.float16):
+        if w.dtype not in (torch.bfloat16, torch.float16) and not (
+                w.dtype == torch.float32 and (BERT_NATIVE_F32 or self.native_f32)):
             return "storage dtype"
         if d % nh or d // nh not in _ops.BERT_HEAD_DIMS or d % 8 or d > 4096 or cfg.intermediate_size % 8:
             return "shape"
@@ -904,7 +906,8 @@ class BertEncoder(nn.Module):
         first column is set, computed on packed tokens by the hand-written forward (bert_ops.hip): no pad token is computed,
         attention is variable-length and non-causal, LayerNorm and GELU are fused kernels, and the LAST block computes K / V for
         every token but Q, attention, the output dense, LayerNorm and FFN for the N CLS rows only.  Returns [N, d], or None to
-        decline (the caller then runs the padded forward): grad enabled, training with dropout, f32 / CPU model, head_dim
+        decline (the caller then runs the padded forward): grad enabled, training with dropout, CPU model, f32 model unless
+        BERT_NATIVE_F32 / native_f32 opts in (the wrappers then run the f32-storage kernels; the GEMMs stay F.linear), head_dim
         outside {32, 64}, a mask that is not 0/1, a row whose first token is masked, ids out of their tables, BERT_NATIVE off.
         Host tensors (what a tokenizer returns) are checked and packed on the host and uploaded once: no device sync."""
         if attention_mask is None or self.native_decline_reason() is not None:
@@ -1055,6 +1058,12 @@ class BertEncoder(nn.Module):
 
 BERT_NATIVE = True       # BertEncoder.pooled_cls runs the packed hand-written forward; False: it declines and the padded PyTorch
 #                          path runs (the A/B arm of tools/bert_encode_bench.py)
+
+
+BERT_NATIVE_F32 = False  # True: BertEncoder.pooled_cls also takes float32 storage (ModelForInference's default dtype) on the f32
+#                          kernels of bert_ops.hip (f32-input MFMA attention, the row kernels on float); False: an f32 model declines
+#                          with "storage dtype" and runs padded, as ever.  `BertEncoder.native_f32` / ModelForInference(packed_f32=
+#                          True) is the same switch for one model.  Forward only: pooled_cls_train has no f32 form.
 
 
 BERT_FUSED_HIDDEN_DROPOUT = False  # True: BertEncoder.pooled_cls_train takes the hidden dropout (embedding output, the two

@@ -246,7 +246,10 @@ class ModelForInference(nn.Module):
         encoder: nn.Module = None,
         config=None,
         tokenizer=None,
+        packed_f32: bool = False,
     ) -> None:
+        """packed_f32: a float32 BERT-family encoder (neither use_fp16 nor use_bf16) runs `encode()` on the packed f32 forward
+        (`BertEncoder.native_f32`) instead of the padded PyTorch path; off by default, ignored for Llama and 16-bit models."""
         super().__init__()
         if use_bf16 and use_fp16:                                     # modeling.py:443-444
             raise ValueError("Cannot use fp16 and bf16 in the same time!")
@@ -272,6 +275,8 @@ class ModelForInference(nn.Module):
         if not getattr(self.tokenizer, "pad_token", None):            # modeling.py:467-468
             raise ValueError("pad_token is not specified!")
         self.model = self.model.to(self.device)
+        if packed_f32 and hasattr(self.model, "native_f32"):
+            self.model.native_f32 = True
 
     @torch.inference_mode()
     def encode(
@@ -324,8 +329,8 @@ class ModelForInference(nn.Module):
                 # block runs for the pooled rows only; None for any other mask.  The tensors are still on the host here.
                 pooled = self.model.pooled_last_token(inputs["input_ids"], inputs["attention_mask"])
             elif mode == "cls" and hasattr(self.model, "pooled_cls"):
-                # BERT / XLM-R in 16-bit storage: the packed hand-written forward returns the CLS rows (host packing, no device
-                # sync); None for anything it declines, which then runs the padded forward below exactly as before
+                # BERT / XLM-R in 16-bit storage (f32 with packed_f32): the packed hand-written forward returns the CLS rows (host
+                # packing, no device sync); None for anything it declines, which then runs the padded forward below exactly as before
                 pooled = self.model.pooled_cls(inputs["input_ids"], inputs["attention_mask"])
             if pooled is not None:
                 emb = ops.pool_normalize(pooled[:, None, :], None, "cls", self.normalize_embeddings)

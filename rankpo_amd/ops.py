@@ -1107,7 +1107,8 @@ def last_query_attn(q, kv, cu, num_kv_heads: int, head_dim: int, scale: float):
 
 
 # ------------------------------------------------------------------------------------------------
-# (9) packed forward of the BERT / XLM-R block (BertEncoder.pooled_cls; no autograd: forward only)
+# (9) packed forward of the BERT / XLM-R block (BertEncoder.pooled_cls; no autograd: forward only).  bf16 / fp16 tensors go to the
+# entries of header section (9), float32 tensors to the f32-storage entries of section (9b).
 # ------------------------------------------------------------------------------------------------
 BIDIR_ATTN_Q_BLOCK = 32      # query rows per work-list entry of rpo_bidir_attn_fwd (the only format the kernel takes)
 BERT_HEAD_DIMS = (32, 64)
@@ -1141,6 +1142,13 @@ def bidir_attn_fwd(q, k, v, cu_q, cu_k, tiles, scale, want_lse: bool = False):
             raise ValueError("bidir_attn_fwd: heads must be contiguous inside a token row")
     out = torch.empty((Tq, nh * hd), dtype=q.dtype, device=q.device)
     lse = torch.empty((nh, Tq), dtype=torch.float32, device=q.device) if want_lse else None
+    if q.dtype == torch.float32:             # f32 storage: the entries of header section (9b)
+        with torch.cuda.device(q.device):
+            check(lib.rpo_bidir_attn_fwd_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(0), k.stride(0), v.stride(0),
+                                             cu_q.data_ptr(), cu_k.data_ptr(), tiles.data_ptr(), tiles.shape[0], tiles.shape[1],
+                                             BIDIR_ATTN_Q_BLOCK, Tq, nh, k.shape[1], hd, float(scale), out.data_ptr(), nh * hd,
+                                             _p(lse), _stream(q)), "rpo_bidir_attn_fwd_f32")
+        return out, lse
     with torch.cuda.device(q.device):
         check(lib.rpo_bidir_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(0), k.stride(0), v.stride(0),
                                      cu_q.data_ptr(), cu_k.data_ptr(), tiles.data_ptr(), tiles.shape[0], tiles.shape[1],
@@ -1159,6 +1167,12 @@ def add_layernorm(a, b, weight, bias, eps, out=None):
     for t in (a, b, out):
         if t is not None and t.stride(1) != 1:
             raise ValueError("add_layernorm: rows must be contiguous")
+    if a.dtype == torch.float32:
+        with torch.cuda.device(a.device):
+            check(lib.rpo_add_layernorm_fwd_f32(a.data_ptr(), a.stride(0), _p(b), b.stride(0) if b is not None else 0,
+                                                weight.data_ptr(), bias.data_ptr(), float(eps), out.data_ptr(), out.stride(0),
+                                                rows, d, _stream(a)), "rpo_add_layernorm_fwd_f32")
+        return out
     with torch.cuda.device(a.device):
         check(lib.rpo_add_layernorm_fwd(a.data_ptr(), a.stride(0), _p(b), b.stride(0) if b is not None else 0,
                                         weight.data_ptr(), bias.data_ptr(), float(eps), out.data_ptr(), out.stride(0), rows, d,
@@ -1171,6 +1185,10 @@ def gelu_(x):
     lib = _lib.load()
     if x.dim() != 2 or x.stride(1) != 1:
         raise ValueError("gelu_: 2-D with contiguous rows")
+    if x.dtype == torch.float32:
+        with torch.cuda.device(x.device):
+            check(lib.rpo_gelu_fwd_f32(x.data_ptr(), x.shape[0], x.shape[1], x.stride(0), _stream(x)), "rpo_gelu_fwd_f32")
+        return x
     with torch.cuda.device(x.device):
         check(lib.rpo_gelu_fwd(x.data_ptr(), x.shape[0], x.shape[1], x.stride(0), _dt(x), _stream(x)), "rpo_gelu_fwd")
     return x
@@ -1185,6 +1203,13 @@ def bert_embed_ln(ids, pos, token_types, word, type_emb, pos_emb, weight, bias, 
         if not t.is_contiguous():
             raise ValueError("bert_embed_ln: embedding tables must be contiguous")
     out = torch.empty((T, d), dtype=word.dtype, device=word.device)
+    if word.dtype == torch.float32:
+        with torch.cuda.device(word.device):
+            check(lib.rpo_bert_embed_ln_fwd_f32(ids.data_ptr(), _p(token_types), pos.data_ptr(), T, word.data_ptr(), word.shape[0],
+                                                type_emb.data_ptr(), type_emb.shape[0], pos_emb.data_ptr(), pos_emb.shape[0],
+                                                weight.data_ptr(), bias.data_ptr(), float(eps), out.data_ptr(), d, d,
+                                                _stream(word)), "rpo_bert_embed_ln_fwd_f32")
+        return out
     with torch.cuda.device(word.device):
         check(lib.rpo_bert_embed_ln_fwd(ids.data_ptr(), _p(token_types), pos.data_ptr(), T, word.data_ptr(), word.shape[0],
                                         type_emb.data_ptr(), type_emb.shape[0], pos_emb.data_ptr(), pos_emb.shape[0],
