@@ -31,6 +31,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from bert_parity_util import attn64 as _attn64     # float64 forward + backward of one sequence, with its absn / absd terms
 from oracle import encoder_ref as E
 
 pytestmark = pytest.mark.gpu
@@ -53,27 +54,6 @@ def _nan(shape, dtype):
 # ------------------------------------------------------------------------------------------------
 # attention backward, with and without dropout
 # ------------------------------------------------------------------------------------------------
-def _attn64(q, k, v, do, scale, keep, p):
-    """float64 forward + backward of one sequence: q/do [lq, nh, hd], k/v [lk, nh, hd], keep [nh, lq, lk] or None.
-    Returns (out, dq, dk, dv) and the norm-with-absolute-values versions of dq, dk, dv."""
-    q, k, v, do = (t.double().transpose(0, 1) for t in (q, k, v, do))          # [nh, l, hd]
-    P = torch.softmax(q @ k.transpose(1, 2) * scale, -1)
-    kp = torch.ones_like(P) if keep is None else keep.double() / (1 - p)
-    Pd = P * kp
-    out = Pd @ v
-    dPd = do @ v.transpose(1, 2)
-    dP = dPd * kp
-    delta = (do * out).sum(-1, keepdim=True)
-    dS = P * (dP - delta)
-    dq, dk, dv = dS @ k * scale, dS.transpose(1, 2) @ q * scale, Pd.transpose(1, 2) @ do
-    delta_abs = (do.abs() * out.abs()).sum(-1, keepdim=True)    # sum |dO| |O| with the reference's own O
-    dSa = P * (dP.abs() + delta_abs)
-    absn = (dSa @ k.abs() * scale, dSa.transpose(1, 2) @ q.abs() * scale, Pd.transpose(1, 2) @ do.abs())
-    # the channel of delta alone: an error e_q of delta moves dq[q] by scale e_q (P K)[q] and dk[k] by scale sum_q P[q, k] e_q Q[q]
-    absd = (delta_abs * (P @ k).abs() * scale, (P * delta_abs).transpose(1, 2) @ q.abs() * scale, None)
-    return (out, dq, dk, dv), absn, absd
-
-
 def _sdpa_ctrl(q, k, v, do, scale):
     """torch's own SDPA forward + backward in the storage dtype, one sequence, no dropout: the control."""
     qs, ks, vs = (t.transpose(0, 1)[None].detach().clone().requires_grad_(True) for t in (q, k, v))
