@@ -546,6 +546,33 @@ int rpo_hidden_dropout_mask(int64_t row0, int64_t rows, int64_t d, float p_drop,
                             unsigned char* mask, rpo_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * (10c) embedding-table gradient of (10) without atomics (rankpo_amd/csrc/embed_grad.hip; opt-in:
+ * encoder.BERT_DETERMINISTIC_EMBED_GRAD).  out [table_rows, d] (row stride ldout) receives, for every table row r that occurs in
+ * the ids, the sum of the rows t of ds [tokens, d] (row stride ldds) with ids[t] == r; the caller zero-fills out, and rows that do
+ * not occur, and row padding_idx (-1: none), are not written.  The ids reach the call as a plan built on the host
+ * (ops.embed_grad_plan), int32 on the device:
+ *   order  [tokens]        the stable ascending sort of the ids (packed-token indices)
+ *   chunks [n_chunks, 4]   (table row, first position in order, rows, slot): every run of equal ids in order (a segment) cut into
+ *                          consecutive chunks from its first row; slot = -1 for the only chunk of its segment, else the chunk's
+ *                          workspace row: a segment's chunks hold consecutive slots in chunk order
+ *   multi  [n_multi, 3]    (table row, first slot, chunks) of every segment with several chunks; n_partials = the slots in all
+ * THE ORDER OF THE SUM IS PART OF THE CONTRACT: a chunk's rows are added one after the other in f32, in ascending packed-token
+ * order, onto 0; a segment of one chunk is then rounded once to the storage dtype and stored; a segment of several chunks stores
+ * its f32 chunk sums to the workspace, and a second launch adds them one after the other in ascending chunk order onto 0 and
+ * rounds once.  No atomics; nothing depends on how blocks are scheduled: equal arguments give equal bits.  Inf / NaN in ds reach
+ * the (row, column) they belong to and no other.  One wave per (chunk, 512-column slice).
+ * bf16 / fp16 (RPO_DT_F32: RPO_ERR_UNSUPPORTED), d % 8 == 0, strides % 8 == 0, 16-byte aligned ds / out / workspace (else
+ * RPO_ERR_UNSUPPORTED); tokens, table_rows <= 2^31 - 1.  workspace: f32, at least rpo_embed_grad_workspace_elems(n_partials, d)
+ * elements (RPO_ERR_WORKSPACE otherwise; NULL when n_partials == 0).  tokens == 0 does nothing.  A plan entry out of range is
+ * skipped (a token index: clamped), never followed outside the buffers.
+ * --------------------------------------------------------------------------------------------- */
+int64_t rpo_embed_grad_workspace_elems(int64_t n_partials, int64_t d);
+int rpo_embed_grad_sorted(const void* ds, int64_t ldds, int64_t tokens, int64_t d, int dtype, const int* order, const int* chunks,
+                          int64_t n_chunks, const int* multi, int64_t n_multi, int64_t n_partials, void* out, int64_t ldout,
+                          int64_t table_rows, int64_t padding_idx, float* workspace, int64_t workspace_elems,
+                          rpo_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * (8) exact top-k over score rows, merged chunk by chunk ("next" row f3: the k-selection of faiss.IndexFlatIP.search,
  * reference src/utils.py:58-80).  scores: [rows, cols] (row stride ld elements) of the chunk whose first column is corpus
  * row col0; best_val f32 [rows, k] / best_idx int64 [rows, k]: the winners so far, best first (value descending, ties by

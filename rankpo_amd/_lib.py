@@ -121,6 +121,9 @@ SIGNATURES = {
     "rpo_layernorm_drop_bwd": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _f32, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _f32,
                                          _u64, _i64, _i64, _vp]),
     "rpo_hidden_dropout_mask": (C.c_int, [_i64, _i64, _i64, _f32, _u64, _i64, _vp, _vp]),
+    "rpo_embed_grad_workspace_elems": (_i64, [_i64, _i64]),
+    "rpo_embed_grad_sorted": (C.c_int, [_vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp,
+                                        _i64, _vp]),
 }
 
 _lib = None

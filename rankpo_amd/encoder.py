@@ -865,7 +865,8 @@ class BertEncoder(nn.Module):
     def _pack_upload(self, input_ids, attention_mask, token_type_ids=None, train: bool = False):
         """Host side shared by `pooled_cls` and `pooled_cls_train`: check and pack the batch (`bert_pack`), check the ids against
         their tables, build the work lists and upload everything as ONE pinned int32 buffer.  None: decline.  train: also the
-        key-side work lists of the attention backward."""
+        key-side work lists of the attention backward and, with BERT_DETERMINISTIC_EMBED_GRAD, the plans of the sorted embedding
+        gradients (`ops.embed_grad_plan` of the word ids, the positions and the token types)."""
         host = lambda t: None if t is None else t.cpu()           # device tensors: one sync here, as the padded path's mask check
         packed = bert_pack(host(input_ids), host(attention_mask), host(token_type_ids),
                            roberta=self.embeddings.roberta_positions, pad_id=self.embeddings.pad_id)
@@ -887,17 +888,27 @@ class BertEncoder(nn.Module):
             tail += [torch.from_numpy(_ops.bidir_attn_key_tile_list(lens, lens)).reshape(-1),
                      torch.from_numpy(_ops.bidir_attn_key_tile_list([1] * N, lens)).reshape(-1)]
         parts = [ids, pos] + ([tts] if tts is not None else []) + tail
+        plans = None
+        if train and BERT_DETERMINISTIC_EMBED_GRAD:                # the sorted embedding gradients' plans ride in the same upload
+            plans = [None if t is None else _ops.embed_grad_plan(t) for t in (ids, pos, tts)]
+            n_head = len(parts)
+            parts = parts + [a for p in plans if p is not None for a in _ops.embed_grad_plan_parts(p)]
         dev = emb.word_embeddings.weight.device
         buf = torch.cat([p.to(torch.int32) for p in parts]).pin_memory().to(dev, non_blocking=True)   # the one upload
         views, o = [], 0
         for p in parts:
             views.append(buf[o:o + p.numel()])
             o += p.numel()
+        if plans is not None:
+            pv = iter(views[n_head:])
+            views = views[:n_head]
+            plans = tuple(None if p is None else _ops.embed_grad_plan_views(p, next(pv), next(pv), next(pv)) for p in plans)
         tv = views[-len(tail):]
         pk = SimpleNamespace(N=N, T=T, lens=lens, ids=views[0], pos=views[1], tts=views[2] if tts is not None else None,
                              cu=tv[0], cu_cls=tv[1], tiles=tv[2].view(-1, 2), tiles_cls=tv[3].view(-1, 2))
         if train:
             pk.k_tiles, pk.k_tiles_cls = tv[4].view(-1, 2), tv[5].view(-1, 2)
+            pk.embed_plans = plans                                # (word, position, token type) or None: the switch is off
         pk.cls_idx = pk.cu[:-1]                                   # the first packed token of every sequence is its CLS token
         return pk
 
@@ -983,7 +994,8 @@ class BertEncoder(nn.Module):
         stateless function of (`ops.bert_hidden_seed(seed)`, site, packed row, column); the seed is then drawn when any attention
         or hidden p > 0.  After `gradient_checkpointing_enable(packed=True)` (train mode) that is forced on and every block runs
         as a non-reentrant `torch.utils.checkpoint` of its input [T, d]: the backward recomputes the block, masks included, from
-        the call's seed, without drawing anything.  Returns [N, d] or None to
+        the call's seed, without drawing anything.  BERT_DETERMINISTIC_EMBED_GRAD: the embedding-table gradients come from
+        `ops.embed_grad_sorted` (plans built here on the host) instead of the atomic scatter.  Returns [N, d] or None to
         decline (`native_train_decline_reason`, a mask / id condition of `pooled_cls`, or a mask that is not right-padded)."""
         if attention_mask is None or self.native_train_decline_reason() is not None:
             return None
@@ -1041,7 +1053,7 @@ class BertEncoder(nn.Module):
         p_emb = p_hid(emb.dropout)
         x = _ops.bert_embed_ln_train(pk.ids, pk.pos, pk.tts, emb.word_embeddings.weight, emb.token_type_embeddings.weight,
                                      emb.position_embeddings.weight, emb.LayerNorm.weight, emb.LayerNorm.bias, emb.LayerNorm.eps,
-                                     emb.word_embeddings.padding_idx, p_emb if fused else 0.0, hseed)
+                                     emb.word_embeddings.padding_idx, p_emb if fused else 0.0, hseed, pk.embed_plans)
         if not fused and p_emb > 0:
             x = _hidden_dropout(x, p_emb)
         if len(layers) == 0:
@@ -1074,6 +1086,14 @@ BERT_FUSED_HIDDEN_DROPOUT = False  # True: BertEncoder.pooled_cls_train takes th
 
 BERT_NATIVE_TRAIN = True  # BertEncoder.pooled_cls_train runs the packed hand-written training step; False: it declines and the
 #                           padded PyTorch path runs, exactly as before (the A/B arm of tools/bert_train_bench.py)
+
+
+BERT_DETERMINISTIC_EMBED_GRAD = False  # True: BertEncoder.pooled_cls_train takes the three embedding-table gradients from
+#                                        `ops.embed_grad_sorted` (embed_grad.hip: per table row one f32 sum in an order fixed by the
+#                                        ids, written once in the storage dtype; plans built on the host inside `_pack_upload`'s one
+#                                        upload) instead of the stock atomic `index_add_` into f32 tables: the whole packed step is
+#                                        then bit-reproducible from its seed, and no f32 table is built.  Agrees with the default
+#                                        within the rounding of two f32 sums; cost: tools/embed_grad_bench.py.
 
 
 def _hidden_dropout(x, p):

@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import threading
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import torch
 
@@ -1127,6 +1128,73 @@ def bidir_attn_tile_list(lens_q, lens_k, q_block: int = BIDIR_ATTN_Q_BLOCK):
     return np.stack([seq, q0], 1).astype(np.int32).reshape(-1, 2)
 
 
+EMBED_GRAD_CHUNK = 32        # rows of ds per work item of rpo_embed_grad_sorted: a table row that T tokens hit is summed by T / 32 waves
+
+
+class EmbedGradPlan(NamedTuple):
+    """`embed_grad_plan`'s result (int32 numpy arrays), or the same with order / chunks / multi on the device (`embed_grad_plan_to`,
+    `BertEncoder._pack_upload`): what `embed_grad_sorted` takes."""
+    order: object        # [T] the stable ascending sort of the ids: packed-token indices
+    seg_ids: object      # [S] the distinct ids, ascending
+    seg_start: object    # [S + 1] segment s = order[seg_start[s]:seg_start[s + 1]], the tokens whose id is seg_ids[s]
+    chunks: object       # [C, 4] (id, first position in order, rows <= chunk, slot): slot = -1 for the only chunk of its segment,
+    #                      else its workspace row; a segment's chunks are consecutive, from its first row, with consecutive slots
+    multi: object        # [M, 3] (id, first slot, chunks) of the segments with several chunks
+    n_partials: int      # slots in all
+
+
+def embed_grad_plan(ids, chunk: int = EMBED_GRAD_CHUNK) -> EmbedGradPlan:
+    """The host plan of `embed_grad_sorted` for the ids [T] of the packed tokens (host tensor or array; the caller has checked them
+    against their table).  It fixes the order of every sum from the ids alone: see `embed_grad_sorted`."""
+    import numpy as np
+    if chunk < 1:
+        raise ValueError("embed_grad_plan: chunk must be >= 1")
+    a = np.asarray(ids, dtype=np.int64).reshape(-1)
+    T = a.shape[0]
+    if T and (int(a.min()) < 0 or int(a.max()) >= 1 << 31):
+        raise ValueError("embed_grad_plan: ids must be table rows, 0 <= id < 2^31")
+    # numpy's stable sort of 16-bit keys is a radix sort: low half, then high half = the stable sort of the whole key, several times
+    # faster than the merge sort it runs on wider keys (the plan is host time in front of the step)
+    order = np.argsort((a & 0xffff).astype(np.uint16), kind="stable")
+    if T and int(a.max()) >= 1 << 16:
+        order = order[np.argsort((a >> 16).astype(np.uint16)[order], kind="stable")]
+    s = a[order]
+    first = np.flatnonzero(np.concatenate([[True], s[1:] != s[:-1]])) if T else np.zeros(0, np.int64)
+    seg_start = np.concatenate([first, [T]]).astype(np.int64)
+    seg_ids = s[first]
+    nch = (np.diff(seg_start) + chunk - 1) // chunk                          # chunks per segment
+    seg_of = np.repeat(np.arange(len(first)), nch)
+    k = np.arange(int(nch.sum())) - np.repeat(np.cumsum(nch) - nch, nch)     # a chunk's index inside its segment
+    start = seg_start[seg_of] + k * chunk
+    rows = np.minimum(chunk, seg_start[seg_of + 1] - start)
+    is_multi = nch > 1
+    held = np.where(is_multi, nch, 0)
+    slot0 = np.cumsum(held) - held
+    slot = np.where(is_multi[seg_of], slot0[seg_of] + k, -1)
+    i32 = lambda x, *shape: np.ascontiguousarray(x, dtype=np.int32).reshape(*shape)
+    return EmbedGradPlan(i32(order, -1), i32(seg_ids, -1), i32(seg_start, -1),
+                         i32(np.stack([seg_ids[seg_of], start, rows, slot], 1), -1, 4),
+                         i32(np.stack([seg_ids[is_multi], slot0[is_multi], nch[is_multi]], 1), -1, 3), int(held.sum()))
+
+
+def embed_grad_plan_parts(plan: EmbedGradPlan):
+    """The arrays of a host plan that the kernel reads, flat, as host int32 tensors: what goes into an upload."""
+    return [torch.from_numpy(plan.order), torch.from_numpy(plan.chunks).reshape(-1), torch.from_numpy(plan.multi).reshape(-1)]
+
+
+def embed_grad_plan_views(plan: EmbedGradPlan, order, chunks, multi) -> EmbedGradPlan:
+    """The plan with the device views of its uploaded parts (flat, as `embed_grad_plan_parts` lists them) in place."""
+    return plan._replace(order=order, chunks=chunks.view(-1, 4), multi=multi.view(-1, 3))
+
+
+def embed_grad_plan_to(plan: EmbedGradPlan, device) -> EmbedGradPlan:
+    """One pinned upload of a host plan (tests, tools; the training step puts its plans into the upload it makes anyway)."""
+    parts = embed_grad_plan_parts(plan)
+    buf = torch.cat(parts).pin_memory().to(device, non_blocking=True)
+    n = [p.numel() for p in parts]
+    return embed_grad_plan_views(plan, buf[:n[0]], buf[n[0]:n[0] + n[1]], buf[n[0] + n[1]:])
+
+
 def bidir_attn_tile_table(lens_q, lens_k, device, q_block: int = BIDIR_ATTN_Q_BLOCK):
     return torch.from_numpy(bidir_attn_tile_list(lens_q, lens_k, q_block)).to(device, non_blocking=True)
 
@@ -1450,11 +1518,40 @@ def add_layernorm_train(a, b, weight, bias, eps, p_drop: float = 0.0, seed: int 
     return _AddLayerNorm.apply(a, b, weight, bias, eps, p_drop, seed, site)
 
 
+def embed_grad_sorted(ds, plan: EmbedGradPlan, table_rows: int, padding_idx=None):
+    """The gradient of an embedding table from ds [T, d] (bf16 / fp16) and the plan of the T ids (`embed_grad_plan`, on ds's device:
+    `embed_grad_plan_to`) -> a new zero-filled [table_rows, d] of ds's dtype with every row that occurs in the ids written once
+    (row `padding_idx` stays zero).  No atomics and no f32 table; the order of every sum follows from the ids alone, so equal
+    inputs give equal bits: per chunk of the plan the rows of ds are added one after the other in f32, in ascending packed-token
+    order, onto 0; an id with one chunk is rounded once; an id with several chunks has its f32 chunk sums added one after the
+    other in chunk order onto 0 (second launch) and rounded once."""
+    lib = _lib.load()
+    T, d = ds.shape
+    if plan.order.shape[0] != T:
+        raise ValueError("embed_grad_sorted: the plan was built for another number of tokens")
+    ds = ds if ds.stride(1) == 1 and ds.stride(0) % 8 == 0 and ds.data_ptr() % 16 == 0 else ds.contiguous()
+    out = torch.zeros((table_rows, d), dtype=ds.dtype, device=ds.device)
+    if T == 0:
+        return out
+    ws_elems = lib.rpo_embed_grad_workspace_elems(plan.n_partials, d)
+    ws = torch.empty((ws_elems,), dtype=torch.float32, device=ds.device) if ws_elems else None
+    with torch.cuda.device(ds.device):
+        check(lib.rpo_embed_grad_sorted(ds.data_ptr(), ds.stride(0), T, d, _dt(ds), plan.order.data_ptr(), plan.chunks.data_ptr(),
+                                        plan.chunks.shape[0], plan.multi.data_ptr() if plan.multi.shape[0] else None,
+                                        plan.multi.shape[0], plan.n_partials, out.data_ptr(), d, table_rows,
+                                        -1 if padding_idx is None else int(padding_idx), _p(ws), ws_elems, _stream(ds)),
+              "rpo_embed_grad_sorted")
+    return out
+
+
 class _BertEmbedLayerNorm(torch.autograd.Function):
-    """`bert_embed_ln` with a backward: the LayerNorm backward kernel, then ds scattered into the three tables."""
+    """`bert_embed_ln` with a backward: the LayerNorm backward kernel, then ds scattered into the three tables.  plans: None, or the
+    `EmbedGradPlan`s (word, position, token type or None) of ids / pos / token_types on the device: the table gradients then come
+    from `embed_grad_sorted`."""
 
     @staticmethod
-    def forward(ctx, ids, pos, token_types, word, type_emb, pos_emb, weight, bias, eps, padding_idx, p_drop=0.0, seed=0):
+    def forward(ctx, ids, pos, token_types, word, type_emb, pos_emb, weight, bias, eps, padding_idx, p_drop=0.0, seed=0,
+                plans=None):
         lib = _lib.load()
         T, d = ids.shape[0], word.shape[1]
         for t in (word, type_emb, pos_emb):
@@ -1479,6 +1576,7 @@ class _BertEmbedLayerNorm(torch.autograd.Function):
         ctx.save_for_backward(s, weight, ids, pos, token_types)
         ctx.eps, ctx.padding_idx = float(eps), padding_idx
         ctx.tables = (word.shape, type_emb.shape, pos_emb.shape)
+        ctx.plans = plans
         return y
 
     @staticmethod
@@ -1489,6 +1587,23 @@ class _BertEmbedLayerNorm(torch.autograd.Function):
         else:
             p_drop, seed, site = ctx.drop
             ds, _, dg, db = layernorm_drop_bwd(s, weight, dy, ctx.eps, p_drop, seed, site_in=site)
+        if ctx.plans is not None:
+            # the deterministic form: every touched table row is one f32 sum in an order fixed by the ids, written once in the
+            # storage dtype (`embed_grad_sorted`); no f32 table
+            p_word, p_pos, p_type = ctx.plans
+            dword = dpos = dtype_emb = None
+            if ctx.needs_input_grad[3]:
+                dword = embed_grad_sorted(ds, p_word, ctx.tables[0][0], ctx.padding_idx)
+            if ctx.needs_input_grad[4]:
+                if token_types is None:                    # type 0 for every token: one row, a deterministic reduction already
+                    dtype_emb = torch.zeros(ctx.tables[1], dtype=s.dtype, device=ds.device)
+                    dtype_emb[0] = ds.float().sum(0).to(s.dtype)
+                else:
+                    dtype_emb = embed_grad_sorted(ds, p_type, ctx.tables[1][0])
+            if ctx.needs_input_grad[5]:
+                dpos = embed_grad_sorted(ds, p_pos, ctx.tables[2][0])
+            return (None, None, None, dword, dtype_emb, dpos, dg.to(weight.dtype), db.to(weight.dtype), None, None, None, None,
+                    None)
         # Embedding gradient = plumbing: stock index_add_ of ds into f32 tables.  It is atomic-based (the order of the adds into one
         # row is not fixed), like the padded path's own embedding backward; every other gradient of the native step is deterministic.
         # Cost: one dense f32 [rows, d] table per embedding and call plus its storage-dtype copy (the word table of XLM-R /
@@ -1513,14 +1628,19 @@ class _BertEmbedLayerNorm(torch.autograd.Function):
             dtype_emb = dtype_emb.to(s.dtype)
         if ctx.needs_input_grad[5]:
             dpos = scatter(ctx.tables[2], pos).to(s.dtype)
-        return None, None, None, dword, dtype_emb, dpos, dg.to(weight.dtype), db.to(weight.dtype), None, None, None, None
+        return None, None, None, dword, dtype_emb, dpos, dg.to(weight.dtype), db.to(weight.dtype), None, None, None, None, None
 
 
 def bert_embed_ln_train(ids, pos, token_types, word, type_emb, pos_emb, weight, bias, eps, padding_idx=None, p_drop: float = 0.0,
-                        seed: int = 0):
+                        seed: int = 0, plans=None):
     """Differentiable `bert_embed_ln` (gradients to the three tables and the LayerNorm parameters).  p_drop > 0: the output is
-    dropped (hidden site 0, `seed`: `bert_hidden_seed` of the call's seed) inside the kernels; p_drop == 0: as before."""
-    return _BertEmbedLayerNorm.apply(ids, pos, token_types, word, type_emb, pos_emb, weight, bias, eps, padding_idx, p_drop, seed)
+    dropped (hidden site 0, `seed`: `bert_hidden_seed` of the call's seed) inside the kernels; p_drop == 0: as before.
+    plans = (word, position, token type or None) `EmbedGradPlan`s of ids / pos / token_types on the device: the table gradients
+    are `embed_grad_sorted`'s (bit-reproducible, no f32 table); None: the stock atomic scatter."""
+    if plans is not None and (len(plans) != 3 or plans[0] is None or plans[1] is None or (plans[2] is None) != (token_types is None)):
+        raise ValueError("bert_embed_ln_train: plans = (word, position, token type) plans, the last None exactly when token_types is")
+    return _BertEmbedLayerNorm.apply(ids, pos, token_types, word, type_emb, pos_emb, weight, bias, eps, padding_idx, p_drop, seed,
+                                     plans)
 
 
 def gelu_out(u):
