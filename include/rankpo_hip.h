@@ -522,6 +522,8 @@ int rpo_gelu_bwd(const void* u, int64_t ldu, const void* dh, int64_t lddh, void*
  * inv_keep = rpo_hidden_dropout_scale(p_drop) = 1 / (1 - p_drop) in f32, the attention kernels' factor.  drop(x) below =
  * round(f32(x) * inv_keep) * keep on a value x of the storage type: the rounding points of a separate dropout pass.
  * bf16 / fp16, d % 8 == 0, d <= 4096, strides % 8 == 0, 16-byte aligned, rows <= 2^31 - 1; rows == 0 does nothing.
+ * The three entries launch the DROP = true instances of the row kernels of (9) / (10) (one template per role, the entries of
+ * (9) / (10) its DROP = false instances).
  *
  * rpo_add_layernorm_drop_fwd: s = round(a + drop(b)) (b required), y = LayerNorm(s); s stored as rpo_add_layernorm_train_fwd does.
  * rpo_bert_embed_ln_drop_fwd: s as rpo_bert_embed_ln_train_fwd, y = drop(round(LayerNorm(s))).

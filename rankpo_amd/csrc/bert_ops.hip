@@ -22,6 +22,9 @@
 // Plain HIP with MFMA builtins; no inline asm, no counted waits.  No atomics: every entry is deterministic.
 #include "common.hpp"
 
+#include <initializer_list>
+#include <type_traits>
+
 namespace {
 
 // ---- storage-type helpers -------------------------------------------------------------------------
@@ -753,22 +756,60 @@ __global__ __launch_bounds__(256) void dropout_mask_kernel(int q_row0, int k_row
     }
 }
 
+// ---- hidden-state dropout inside the row kernels (their DROP = true instances) -------------------------
+// keep(seed, site, packed row, column): the attention dropout's stateless function with (site, row, column) in the places of
+// (head, query row, key row): key = dropout_key(seed, site), bits = dropout_bits(key, row, column >> 2), one 16-bit field per
+// column of the group of 4, KEPT when field >= thr = round(p_drop * 65536).  A lane's 16-byte vector (8 columns) takes two Philox
+// evaluations.  site 0 = the embedding output, 1 + 2 i / 2 + 2 i = the two `dropout(dense(..))` of block i; the seed is
+// ops.bert_hidden_seed(call seed), which no block's attention seed equals.  A recomputed forward (gradient checkpointing) and the
+// backward evaluate the function again: no mask is stored and no generator state is kept.
+// Rounding points are those of the unfused path, x -> round(f32(x) * inv_keep) * keep on stored values: the dense output before
+// the add (add + LayerNorm), the ROUNDED LayerNorm output (embedding), the rounded ds (backward, towards the dense output).
+__device__ __forceinline__ bool hidden_keep(uint64_t seed, int site, int row, int col, unsigned thr) {
+    return dropout_field_keep(dropout_bits(dropout_key(seed, site), row, col >> 2), col, thr);
+}
+// t <- round(t * inv_keep) * keep for the 8 columns c0 .. c0 + 7 (c0 % 8 == 0) of one row; key = dropout_key(seed, site)
+template <typename T>
+__device__ __forceinline__ void hidden_drop8(Vec16<T>& t, unsigned key, int row, int c0, unsigned thr, float inv_keep) {
+    static_assert(Elem<T>::kVec == 8, "the DROP = true instances are the 16-bit ones");
+    const DropBits lo = dropout_bits(key, row, c0 >> 2), hi = dropout_bits(key, row, (c0 >> 2) + 1);
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+        t.v[e] = Elem<T>::round(t.v[e] * inv_keep) * (dropout_field_keep(e < 4 ? lo : hi, c0 + e, thr) ? 1.f : 0.f);
+}
+// what a DROP = true instance reads (a DROP = false one reads none of it): site = the forwards' site and the backward's site_out,
+// site_in = the backward's only
+struct RowDrop {
+    unsigned thr = 0;
+    float inv_keep = 1.0f;
+    uint64_t seed = 0;
+    int site = 0, site_in = -1;
+};
+
 // ---- (2)-(4) row kernels: one wave per row, NV 16-byte vectors per lane ------------------------------
+// A row lies in registers as Vec16<T> x[NV]: columns V (lane + 64 j) .. + V - 1, V = Elem<T>::kVec = elements per 16 bytes (8, or
+// 4 for f32 storage).
 constexpr int kRowThreads = 256;
 
-// y = (x - mean) rstd gamma + beta over a row held in registers (columns V (lane + 64 j) .. + V - 1, V = Elem<T>::kVec = elements
-// per 16 bytes: 8, or 4 for f32 storage), statistics in f32, rounded once
+// mean and rstd of the row in f32, in ONE fixed order (forward and backward take the same two numbers from the same s).
+// sum = the lane's part of the row sum, its vectors added in the order j, then e: lane_sum, or vec_sum beside the loads.
+template <typename T>
+__device__ __forceinline__ void vec_sum(const Vec16<T>& v, float& sum) {
+#pragma unroll
+    for (int e = 0; e < Elem<T>::kVec; ++e) sum += v.v[e];
+}
 template <typename T, int NV>
-__device__ __forceinline__ void layernorm_store(Vec16<T> (&x)[NV], const T* __restrict__ gamma, const T* __restrict__ beta,
-                                                float eps, T* __restrict__ y, int d, int lane) {
-    constexpr int V = Elem<T>::kVec;
+__device__ __forceinline__ float lane_sum(const Vec16<T> (&x)[NV], int d, int lane) {
     float sum = 0.f;
 #pragma unroll
     for (int j = 0; j < NV; ++j)
-        if (V * (lane + 64 * j) < d)
-#pragma unroll
-            for (int e = 0; e < V; ++e) sum += x[j].v[e];
-    const float mean = wave_sum(sum) / (float)d;
+        if (Elem<T>::kVec * (lane + 64 * j) < d) vec_sum<T>(x[j], sum);
+    return sum;
+}
+template <typename T, int NV>
+__device__ __forceinline__ void row_stats(const Vec16<T> (&x)[NV], float sum, float eps, int d, int lane, float& mean, float& rstd) {
+    constexpr int V = Elem<T>::kVec;
+    mean = wave_sum(sum) / (float)d;
     float sq = 0.f;
 #pragma unroll
     for (int j = 0; j < NV; ++j)
@@ -778,7 +819,18 @@ __device__ __forceinline__ void layernorm_store(Vec16<T> (&x)[NV], const T* __re
                 const float c = x[j].v[e] - mean;
                 sq = fmaf(c, c, sq);
             }
-    const float rstd = rsqrtf(wave_sum(sq) / (float)d + eps);
+    rstd = rsqrtf(wave_sum(sq) / (float)d + eps);
+}
+// y = (x - mean) rstd gamma + beta, rounded once as it is stored.  A DROP = false instance stores each vector as it is normalised.
+// A DROP = true instance leaves the f32 results in x and stores in a pass of its own (which keeps the NV = 8 add + LayerNorm at
+// 96 VGPRs = 5 waves per SIMD); DROP_Y (the embedding) drops in that pass: the value as it would be stored, rounded, then
+// y = round(that * inv_keep) * keep(site) of row `row`.
+template <typename T, int NV, bool DROP, bool DROP_Y>
+__device__ __forceinline__ void layernorm_store(Vec16<T> (&x)[NV], const T* __restrict__ gamma, const T* __restrict__ beta,
+                                                float eps, T* __restrict__ y, int d, int lane, int row, const RowDrop& drop) {
+    constexpr int V = Elem<T>::kVec;
+    float mean, rstd;
+    row_stats<T, NV>(x, lane_sum<T, NV>(x, d, lane), eps, d, lane, mean, rstd);
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
         const int c0 = V * (lane + 64 * j);
@@ -788,45 +840,66 @@ __device__ __forceinline__ void layernorm_store(Vec16<T> (&x)[NV], const T* __re
             bw.load(beta + c0);
 #pragma unroll
             for (int e = 0; e < V; ++e) x[j].v[e] = fmaf((x[j].v[e] - mean) * rstd, gw.v[e], bw.v[e]);
-            x[j].store(y + c0);
+            if constexpr (!DROP) x[j].store(y + c0);
+        }
+    }
+    if constexpr (DROP) {
+        const unsigned key = dropout_key(drop.seed, drop.site);
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int c0 = V * (lane + 64 * j);
+            if (c0 < d) {
+                if constexpr (DROP_Y) {
+#pragma unroll
+                    for (int e = 0; e < V; ++e) x[j].v[e] = Elem<T>::round(x[j].v[e]);
+                    hidden_drop8<T>(x[j], key, row, c0, drop.thr, drop.inv_keep);
+                }
+                x[j].store(y + c0);
+            }
         }
     }
 }
 
-template <typename T, int NV>
+// s = round(a + b), y = LayerNorm(s).  DROP = false: b may be null (s = a) and s is stored where s_out is given (training: the
+// backward recomputes the statistics from it).  DROP = true: s = round(a + round(b * inv_keep) * keep(site)); b and s_out required.
+template <typename T, int NV, bool DROP>
 __global__ __launch_bounds__(kRowThreads) void add_layernorm_kernel(const T* __restrict__ a, int64_t lda, const T* __restrict__ b,
                                                                      int64_t ldb, const T* __restrict__ gamma,
                                                                      const T* __restrict__ beta, float eps, T* __restrict__ y,
                                                                      int64_t ldy, T* __restrict__ s_out, int64_t lds,
-                                                                     int64_t rows, int d) {
+                                                                     int64_t rows, int d, RowDrop drop) {
     const int64_t row = (int64_t)blockIdx.x * (kRowThreads / 64) + (threadIdx.x >> 6);
     constexpr int V = Elem<T>::kVec;
     const int lane = threadIdx.x & 63;
     if (row >= rows) return;
+    const unsigned key = DROP ? dropout_key(drop.seed, drop.site) : 0u;
     Vec16<T> x[NV];
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
         const int c0 = V * (lane + 64 * j);
         if (c0 < d) {
             x[j].load(a + row * lda + c0);
-            if (b) {
+            if (DROP || b) {
                 Vec16<T> t;
                 t.load(b + row * ldb + c0);
+                if constexpr (DROP) hidden_drop8<T>(t, key, (int)row, c0, drop.thr, drop.inv_keep);
 #pragma unroll
                 for (int e = 0; e < V; ++e) x[j].v[e] = Elem<T>::round(x[j].v[e] + t.v[e]);   // the reference's rounded sum
             }
-            if (s_out) x[j].store(s_out + row * lds + c0);   // training: the backward recomputes the statistics from it
+            if (DROP || s_out) x[j].store(s_out + row * lds + c0);
         }
     }
-    layernorm_store<T, NV>(x, gamma, beta, eps, y + row * ldy, d, lane);
+    layernorm_store<T, NV, DROP, false>(x, gamma, beta, eps, y + row * ldy, d, lane, (int)row, drop);
 }
 
-template <typename T, int NV>
+// s = round(round(word + type) + position), y = LayerNorm(s); s stored where s_out is given.  DROP = true (s_out required):
+// y = round(round(LayerNorm(s)) * inv_keep) * keep(site), the dropout of the LayerNorm output as it would be stored.
+template <typename T, int NV, bool DROP>
 __global__ __launch_bounds__(kRowThreads) void bert_embed_ln_kernel(
     const int* __restrict__ ids, const int* __restrict__ tts, const int* __restrict__ pos, int64_t tokens,
     const T* __restrict__ word, int64_t vocab, const T* __restrict__ temb, int64_t ntypes, const T* __restrict__ pemb,
     int64_t npos, const T* __restrict__ gamma, const T* __restrict__ beta, float eps, T* __restrict__ y, int64_t ldy, T* __restrict__ s_out,
-    int64_t lds, int d) {
+    int64_t lds, int d, RowDrop drop) {
     const int64_t row = (int64_t)blockIdx.x * (kRowThreads / 64) + (threadIdx.x >> 6);
     constexpr int V = Elem<T>::kVec;
     const int lane = threadIdx.x & 63;
@@ -847,11 +920,14 @@ __global__ __launch_bounds__(kRowThreads) void bert_embed_ln_kernel(
             p.load(pemb + pi * d + c0);
 #pragma unroll
             for (int e = 0; e < V; ++e) x[j].v[e] = Elem<T>::round(Elem<T>::round(x[j].v[e] + t.v[e]) + p.v[e]);   // (w + t) + p
-            if (s_out) x[j].store(s_out + row * lds + c0);
+            if (DROP || s_out) x[j].store(s_out + row * lds + c0);
         }
     }
-    layernorm_store<T, NV>(x, gamma, beta, eps, y + row * ldy, d, lane);
+    layernorm_store<T, NV, DROP, DROP>(x, gamma, beta, eps, y + row * ldy, d, lane, (int)row, drop);
 }
+
+// exact erf GELU (HF's "gelu"), shared by the in-place and the out-of-place kernel
+__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
 
 template <typename T>
 __global__ __launch_bounds__(256) void gelu_kernel(T* __restrict__ x, int64_t rows, int64_t cols, int64_t ld) {
@@ -863,7 +939,7 @@ __global__ __launch_bounds__(256) void gelu_kernel(T* __restrict__ x, int64_t ro
         Vec16<T> t;
         t.load(p);
 #pragma unroll
-        for (int e = 0; e < V; ++e) t.v[e] = 0.5f * t.v[e] * (1.0f + erff(t.v[e] * 0.70710678118654752f));
+        for (int e = 0; e < V; ++e) t.v[e] = gelu_erf(t.v[e]);
         t.store(p);
     }
 }
@@ -873,54 +949,51 @@ __global__ __launch_bounds__(256) void gelu_kernel(T* __restrict__ x, int64_t ro
 // per block; wave w of block b walks rows 4 b + w, + 4 gridDim.x, .. with the row in registers and adds dy xhat / dy into per-lane
 // f32 sums in that fixed order; the block's four waves then add their sums through LDS in wave order 0, 1, 2, 3 and the last one
 // writes dgamma_partial / dbeta_partial [gridDim.x, d], summed by the caller (the dw_partial pattern of rpo_add_rmsnorm_bwd).
+// DROP = true adds the dropout of the fused forwards, each a run-time condition: site_in >= 0: dy <- round(dy * inv_keep) *
+// keep(site_in) as it is loaded (the embedding: dropout AFTER the LayerNorm); db_out != nullptr: db = round(round(ds) * inv_keep) *
+// keep(site) beside ds (add + LayerNorm: ds to a, db to the dense output b).  DROP = false reads neither db_out nor drop.
 constexpr int kLnBwdMaxBlocks = 1024;
 constexpr int kLnBwdWaves = 4;
 
-template <typename T, int NV>
-__global__ __launch_bounds__(64 * kLnBwdWaves) void layernorm_bwd_kernel(const T* __restrict__ s, int64_t lds, const T* __restrict__ gamma,
-                                                           const T* __restrict__ dy, int64_t lddy, float eps, T* __restrict__ ds,
-                                                           int64_t ldds, float* __restrict__ dgp, float* __restrict__ dbp,
-                                                           int64_t rows, int d) {
+template <typename T, int NV, bool DROP>
+__global__ __launch_bounds__(64 * kLnBwdWaves) void layernorm_bwd_kernel(
+    const T* __restrict__ s, int64_t lds, const T* __restrict__ gamma, const T* __restrict__ dy, int64_t lddy, float eps,
+    T* __restrict__ ds, int64_t ldds, float* __restrict__ dgp, float* __restrict__ dbp, int64_t rows, int d,
+    T* __restrict__ db_out, int64_t lddb, RowDrop drop) {
     extern __shared__ float ln_red[];       // [2][d]: the block's dgamma | dbeta sums
+    constexpr int V = Elem<T>::kVec;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float dg[NV][8], db[NV][8];
+    const unsigned key_in = DROP ? dropout_key(drop.seed, drop.site_in) : 0u, key_out = DROP ? dropout_key(drop.seed, drop.site) : 0u;
+    float dg[NV][V], db[NV][V];
     Vec16<T> gw[NV];
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) dg[j][e] = db[j][e] = 0.f;
-        if (8 * (lane + 64 * j) < d) gw[j].load(gamma + 8 * (lane + 64 * j));
+        for (int e = 0; e < V; ++e) dg[j][e] = db[j][e] = 0.f;
+        if (V * (lane + 64 * j) < d) gw[j].load(gamma + V * (lane + 64 * j));
     }
     for (int64_t row = (int64_t)blockIdx.x * kLnBwdWaves + wave; row < rows; row += (int64_t)gridDim.x * kLnBwdWaves) {
         Vec16<T> x[NV], g[NV];
         float sum = 0.f;
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
-            const int c0 = 8 * (lane + 64 * j);
+            const int c0 = V * (lane + 64 * j);
             if (c0 < d) {
                 x[j].load(s + row * lds + c0);
                 g[j].load(dy + row * lddy + c0);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) sum += x[j].v[e];
+                if constexpr (DROP)
+                    if (drop.site_in >= 0) hidden_drop8<T>(g[j], key_in, (int)row, c0, drop.thr, drop.inv_keep);
+                vec_sum<T>(x[j], sum);
             }
         }
-        const float mean = wave_sum(sum) / (float)d;
-        float sq = 0.f;
-#pragma unroll
-        for (int j = 0; j < NV; ++j)
-            if (8 * (lane + 64 * j) < d)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float c = x[j].v[e] - mean;
-                    sq = fmaf(c, c, sq);
-                }
-        const float rstd = rsqrtf(wave_sum(sq) / (float)d + eps);
+        float mean, rstd;
+        row_stats<T, NV>(x, sum, eps, d, lane, mean, rstd);
         float c1 = 0.f, c2 = 0.f;
 #pragma unroll
         for (int j = 0; j < NV; ++j)
-            if (8 * (lane + 64 * j) < d)
+            if (V * (lane + 64 * j) < d)
 #pragma unroll
-                for (int e = 0; e < 8; ++e) {
+                for (int e = 0; e < V; ++e) {
                     const float xh = (x[j].v[e] - mean) * rstd, dyv = g[j].v[e], gg = dyv * gw[j].v[e];
                     dg[j][e] = fmaf(dyv, xh, dg[j][e]);
                     db[j][e] += dyv;
@@ -933,11 +1006,18 @@ __global__ __launch_bounds__(64 * kLnBwdWaves) void layernorm_bwd_kernel(const T
         c2 = wave_sum(c2) / (float)d;
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
-            const int c0 = 8 * (lane + 64 * j);
+            const int c0 = V * (lane + 64 * j);
             if (c0 < d) {
 #pragma unroll
-                for (int e = 0; e < 8; ++e) g[j].v[e] = rstd * (g[j].v[e] - c1 - x[j].v[e] * c2);
+                for (int e = 0; e < V; ++e) g[j].v[e] = rstd * (g[j].v[e] - c1 - x[j].v[e] * c2);
                 g[j].store(ds + row * ldds + c0);
+                if constexpr (DROP)
+                    if (db_out) {
+#pragma unroll
+                        for (int e = 0; e < V; ++e) g[j].v[e] = Elem<T>::round(g[j].v[e]);      // ds as stored
+                        hidden_drop8<T>(g[j], key_out, (int)row, c0, drop.thr, drop.inv_keep);
+                        g[j].store(db_out + row * lddb + c0);
+                    }
             }
         }
     }
@@ -945,14 +1025,14 @@ __global__ __launch_bounds__(64 * kLnBwdWaves) void layernorm_bwd_kernel(const T
         if (wave == w) {
 #pragma unroll
             for (int j = 0; j < NV; ++j) {
-                const int c0 = 8 * (lane + 64 * j);
+                const int c0 = V * (lane + 64 * j);
                 if (c0 < d) {
                     float* gl = ln_red + c0;
                     float* bl = ln_red + d + c0;
                     float* gp = dgp + (int64_t)blockIdx.x * d + c0;
                     float* bp = dbp + (int64_t)blockIdx.x * d + c0;
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) {
+                    for (int e = 0; e < V; ++e) {
                         const float a = w == 0 ? dg[j][e] : gl[e] + dg[j][e];
                         const float b = w == 0 ? db[j][e] : bl[e] + db[j][e];
                         if (w == kLnBwdWaves - 1) {
@@ -980,7 +1060,7 @@ __global__ __launch_bounds__(256) void gelu_out_kernel(const T* __restrict__ u, 
         Vec16<T> t;
         t.load(u + rr * ldu + c);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) t.v[e] = 0.5f * t.v[e] * (1.0f + erff(t.v[e] * 0.70710678118654752f));
+        for (int e = 0; e < 8; ++e) t.v[e] = gelu_erf(t.v[e]);
         t.store(hh + rr * ldh + c);
     }
 }
@@ -1011,33 +1091,131 @@ __global__ __launch_bounds__(256) void gelu_bwd_kernel(const T* __restrict__ u, 
     }
 }
 
-int row_vectors(int64_t d) {                // NV of the row kernels: 1, 2, 4 or 8 (d <= 4096); 0 = too wide
-    const int64_t nv = rpo_cdiv(d, 512);
-    return nv <= 1 ? 1 : nv <= 2 ? 2 : nv <= 4 ? 4 : nv <= 8 ? 8 : 0;
+// the keep mask of rows row0 .. row0 + rows - 1, columns 0 .. d - 1 of one site: mask[row][column] (tests and diagnostics)
+__global__ __launch_bounds__(256) void hidden_dropout_mask_kernel(int row0, int rows, int d, int site, unsigned thr, uint64_t seed,
+                                                                  unsigned char* __restrict__ mask) {
+    const int64_t n = (int64_t)rows * d;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        mask[i] = hidden_keep(seed, site, row0 + (int)(i / d), (int)(i % d), thr) ? 1 : 0;
+}
+
+// ---- host side: the argument checks and the dispatch that the entries share -----------------------------
+// An entry answers INVALID_ARG before UNSUPPORTED.  Each helper returns the status of ONE group of arguments; first_error keeps
+// that order over the groups of an entry.
+int first_error(std::initializer_list<int> groups) {
+    int rc = RPO_OK;
+    for (const int s : groups) {
+        if (s == RPO_ERR_INVALID_ARG) return s;
+        if (s != RPO_OK) rc = s;
+    }
+    return rc;
+}
+// NV of the row kernels: 1, 2, 4 or 8 vectors of 8 elements, up to 16 of 4 on f32 storage (d <= 4096); 0 = too wide
+int row_vectors(int64_t d, bool f32) {
+    const int64_t nv = rpo_cdiv(d, f32 ? 256 : 512);
+    return nv <= 1 ? 1 : nv <= 2 ? 2 : nv <= 4 ? 4 : nv <= 8 ? 8 : (f32 && nv <= 16) ? 16 : 0;
+}
+// rows x d of a row entry; nv = 0: too wide.  dtype is the entry's argument, or RPO_DT_F32 from an _f32 entry (f32_entry): the
+// 16-bit entries answer RPO_DT_F32 with UNSUPPORTED.
+int row_shape(int64_t rows, int64_t d, int dtype, bool f32_entry, int nv) {
+    if (rows < 0 || d <= 0 || !rpo_dtype_ok(dtype)) return RPO_ERR_INVALID_ARG;
+    return ((dtype == RPO_DT_F32) != f32_entry || d % 8 || nv == 0) ? RPO_ERR_UNSUPPORTED : RPO_OK;
+}
+// a [rows, d] operand with row stride ld; vec = elements per 16 bytes
+int row_operand(const void* p, int64_t ld, int64_t d, int vec) {
+    if (!p || ld < d) return RPO_ERR_INVALID_ARG;
+    return (!rpo_aligned16(p) || ld % vec) ? RPO_ERR_UNSUPPORTED : RPO_OK;
+}
+// gamma, beta, an embedding table
+int vec_operand(const void* p) { return !p ? RPO_ERR_INVALID_ARG : !rpo_aligned16(p) ? RPO_ERR_UNSUPPORTED : RPO_OK; }
+int embed_tables(const int* ids, const int* pos, const void* word, int64_t vocab, const void* type_emb, int64_t n_types,
+                 const void* pos_emb, int64_t n_pos) {
+    if (!ids || !pos || vocab <= 0 || n_types <= 0 || n_pos <= 0) return RPO_ERR_INVALID_ARG;
+    return first_error({vec_operand(word), vec_operand(type_emb), vec_operand(pos_emb)});
+}
+
+bool attn_common_ok(int64_t num_heads, int64_t num_kv_heads, int64_t head_dim, int dtype, int64_t tile_cols, int64_t block,
+                    int64_t ntiles) {
+    return !(dtype == RPO_DT_F32 || (head_dim != 32 && head_dim != 64) || num_heads != num_kv_heads || tile_cols != 2 ||
+             block != kAttnQBlock || ntiles > 0x7fffffff || num_heads > 65535);
+}
+bool dropout_args(float p_drop, unsigned* thr, float* inv_keep) {      // false: p_drop outside [0, 1)
+    if (!(p_drop >= 0.f) || !(p_drop < 1.f)) return false;
+    *thr = (unsigned)lrintf(p_drop * 65536.f);
+    *inv_keep = 1.0f / (1.0f - p_drop);
+    return true;
+}
+// thr / inv_keep of the row kernels: p_drop below 2^-17 quantises to thr = 0 = no dropout, and then nothing is scaled either
+bool hidden_dropout_args(float p_drop, unsigned* thr, float* inv_keep) {
+    if (!dropout_args(p_drop, thr, inv_keep)) return false;
+    if (*thr == 0) *inv_keep = 1.0f;
+    return true;
+}
+constexpr int64_t kHiddenMaxSite = 1 << 20;     // a site is a small layer index; the bound only keeps it an int
+// dropout and site of a drop entry -> *drop.  Only these entries bound rows: the keep function takes the row as an int.
+int drop_args(int64_t rows, float p_drop, uint64_t seed, int64_t site, RowDrop* drop) {
+    if (rows > 0x7fffffff || site < 0 || site > kHiddenMaxSite || !hidden_dropout_args(p_drop, &drop->thr, &drop->inv_keep))
+        return RPO_ERR_INVALID_ARG;
+    drop->seed = seed;
+    drop->site = (int)site;
+    return RPO_OK;
+}
+
+// f(TypeTag<T>) with T from dtype; F32 = false leaves float out of the instances (the 16-bit entries never reach it)
+template <typename T> struct TypeTag { using type = T; };
+template <bool F32, typename F> void dtype_dispatch(int dtype, F f) {
+    if (dtype == RPO_DT_BF16) f(TypeTag<bf16_t>{});
+    else if (dtype == RPO_DT_F16) f(TypeTag<f16_t>{});
+    else if constexpr (F32) f(TypeTag<float>{});
+}
+// f(integral_constant<NV>) with NV = nv from row_vectors; 16 exists on f32 storage only
+template <typename T, typename F> void nv_dispatch(int nv, F f) {
+    if (nv == 1) f(std::integral_constant<int, 1>{});
+    else if (nv == 2) f(std::integral_constant<int, 2>{});
+    else if (nv == 4) f(std::integral_constant<int, 4>{});
+    else if (sizeof(T) != 4 || nv == 8) f(std::integral_constant<int, 8>{});
+    else if constexpr (sizeof(T) == 4) f(std::integral_constant<int, 16>{});
 }
 
 }  // namespace
 
-#define RPO_ROW_DISPATCH(KERNEL, T, NV, GRID, ST, ...)                                                          \
-    do {                                                                                                        \
-        if (NV == 1) RPO_LAUNCH((KERNEL<T, 1>), GRID, dim3(kRowThreads), 0, ST, __VA_ARGS__);                   \
-        else if (NV == 2) RPO_LAUNCH((KERNEL<T, 2>), GRID, dim3(kRowThreads), 0, ST, __VA_ARGS__);              \
-        else if (NV == 4) RPO_LAUNCH((KERNEL<T, 4>), GRID, dim3(kRowThreads), 0, ST, __VA_ARGS__);              \
-        else RPO_LAUNCH((KERNEL<T, 8>), GRID, dim3(kRowThreads), 0, ST, __VA_ARGS__);                           \
+// launch KERNEL<T> resp. KERNEL<T, NV, DROP>: T from DTYPE (F32: float included), NV from row_vectors; the arguments may name T
+#define RPO_TYPE_DISPATCH(F32, DTYPE, KERNEL, GRID, BLOCK, LDS, ST, ...)               \
+    dtype_dispatch<F32>(DTYPE, [&](auto tag_) {                                        \
+        using T = typename decltype(tag_)::type;                                       \
+        RPO_LAUNCH(KERNEL<T>, GRID, BLOCK, LDS, ST, __VA_ARGS__);                      \
+    })
+#define RPO_ROW_DISPATCH(F32, DTYPE, NV, KERNEL, DROP, GRID, BLOCK, LDS, ST, ...)                                     \
+    dtype_dispatch<F32>(DTYPE, [&](auto tag_) {                                                                       \
+        using T = typename decltype(tag_)::type;                                                                      \
+        nv_dispatch<T>(NV, [&](auto nv_) {                                                                            \
+            RPO_LAUNCH((KERNEL<T, decltype(nv_)::value, DROP>), GRID, BLOCK, LDS, ST, __VA_ARGS__);                   \
+        });                                                                                                           \
+    })
+#define RPO_ATTN_DISPATCH(LAUNCH)                           \
+    do {                                                    \
+        if (dtype == RPO_DT_BF16) {                         \
+            if (head_dim == 32) LAUNCH(bf16_t, 32);         \
+            else LAUNCH(bf16_t, 64);                        \
+        } else {                                            \
+            if (head_dim == 32) LAUNCH(f16_t, 32);          \
+            else LAUNCH(f16_t, 64);                         \
+        }                                                   \
     } while (0)
 
-extern "C" int rpo_bidir_attn_fwd(const void* q, const void* k, const void* v, int64_t q_stride, int64_t k_stride,
-                                  int64_t v_stride, const int* cu_seqlens_q, const int* cu_seqlens_k, const int* tiles,
-                                  int64_t ntiles, int64_t tile_cols, int64_t q_block, int64_t total_q, int64_t num_heads,
-                                  int64_t num_kv_heads, int64_t head_dim, int dtype, float scale, void* out,
-                                  int64_t out_stride, float* lse, rpo_stream_t stream) {
+namespace {
+
+// rpo_bidir_attn_fwd (thr = 0, lse may be null) and rpo_bidir_attn_train_fwd: thr > 0 takes the DROP = true instance
+int bidir_attn_fwd_launch(const void* q, const void* k, const void* v, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                          const int* cu_seqlens_q, const int* cu_seqlens_k, const int* tiles, int64_t ntiles, int64_t tile_cols,
+                          int64_t q_block, int64_t total_q, int64_t num_heads, int64_t num_kv_heads, int64_t head_dim, int dtype,
+                          float scale, void* out, int64_t out_stride, float* lse, unsigned thr, float inv_keep, uint64_t seed,
+                          rpo_stream_t stream) {
     if (!q || !k || !v || !cu_seqlens_q || !cu_seqlens_k || !tiles || !out || ntiles < 0 || total_q <= 0 || num_heads <= 0 ||
         num_kv_heads <= 0 || head_dim <= 0 || !rpo_dtype_ok(dtype) || q_stride <= 0 || k_stride <= 0 || v_stride <= 0 ||
         out_stride <= 0)
         return RPO_ERR_INVALID_ARG;
-    if (dtype == RPO_DT_F32 || (head_dim != 32 && head_dim != 64) || num_heads != num_kv_heads || tile_cols != 2 ||
-        q_block != kAttnQBlock || ntiles > 0x7fffffff || num_heads > 65535)
-        return RPO_ERR_UNSUPPORTED;
+    if (!attn_common_ok(num_heads, num_kv_heads, head_dim, dtype, tile_cols, q_block, ntiles)) return RPO_ERR_UNSUPPORTED;
     if (!rpo_aligned16(q) || !rpo_aligned16(k) || !rpo_aligned16(v) || (reinterpret_cast<uintptr_t>(out) & 7) || q_stride % 8 ||
         k_stride % 8 || v_stride % 8 || out_stride % 4)
         return RPO_ERR_UNSUPPORTED;
@@ -1045,50 +1223,81 @@ extern "C" int rpo_bidir_attn_fwd(const void* q, const void* k, const void* v, i
     const dim3 grid((unsigned)ntiles, (unsigned)num_heads), block(64);
     hipStream_t st = (hipStream_t)stream;
     const float sl = scale * 1.4426950408889634f;
-#define RPO_BIDIR(T, HD)                                                                                                         \
-    RPO_LAUNCH((bidir_attn_fwd_kernel<T, HD, false>), grid, block, 0, st, (const T*)q, (const T*)k, (const T*)v, q_stride,      \
-               k_stride, v_stride, cu_seqlens_q, cu_seqlens_k, tiles, sl, (T*)out, out_stride, lse, total_q, 0u, 1.0f, (uint64_t)0)
-    if (dtype == RPO_DT_BF16) {
-        if (head_dim == 32) RPO_BIDIR(bf16_t, 32);
-        else RPO_BIDIR(bf16_t, 64);
-    } else {
-        if (head_dim == 32) RPO_BIDIR(f16_t, 32);
-        else RPO_BIDIR(f16_t, 64);
-    }
+#define RPO_BIDIR_ARGS(T)                                                                                                    \
+    grid, block, 0, st, (const T*)q, (const T*)k, (const T*)v, q_stride, k_stride, v_stride, cu_seqlens_q, cu_seqlens_k, tiles, \
+        sl, (T*)out, out_stride, lse, total_q
+#define RPO_BIDIR(T, HD)                                                                                           \
+    do {                                                                                                           \
+        if (thr > 0) RPO_LAUNCH((bidir_attn_fwd_kernel<T, HD, true>), RPO_BIDIR_ARGS(T), thr, inv_keep, seed);     \
+        else RPO_LAUNCH((bidir_attn_fwd_kernel<T, HD, false>), RPO_BIDIR_ARGS(T), 0u, 1.0f, (uint64_t)0);          \
+    } while (0)
+    RPO_ATTN_DISPATCH(RPO_BIDIR);
 #undef RPO_BIDIR
+#undef RPO_BIDIR_ARGS
     return rpo_launch_status();
+}
+
+// the add + LayerNorm entries.  train: s is stored (required); DROP: b is required and drop / drop_rc come from drop_args
+template <bool F32, bool DROP>
+int add_layernorm(const void* a, int64_t lda, const void* b, int64_t ldb, const void* gamma, const void* beta, float eps, void* y,
+                  int64_t ldy, void* s, int64_t lds, bool train, int64_t rows, int64_t d, int dtype, int drop_rc, RowDrop drop,
+                  rpo_stream_t stream) {
+    const int vec = F32 ? 4 : 8, nv = row_vectors(d, F32);
+    const int rc = first_error({row_shape(rows, d, dtype, F32, nv), row_operand(a, lda, d, vec),
+                                (DROP || b) ? row_operand(b, ldb, d, vec) : RPO_OK, vec_operand(gamma), vec_operand(beta),
+                                row_operand(y, ldy, d, vec), train ? row_operand(s, lds, d, vec) : RPO_OK, drop_rc});
+    if (rc != RPO_OK || rows == 0) return rc;
+    RPO_ROW_DISPATCH(F32, dtype, nv, add_layernorm_kernel, DROP, dim3((unsigned)rpo_cdiv(rows, kRowThreads / 64)), dim3(kRowThreads),
+                     0, (hipStream_t)stream, (const T*)a, lda, (const T*)b, ldb, (const T*)gamma, (const T*)beta, eps, (T*)y, ldy,
+                     (T*)s, lds, rows, (int)d, drop);
+    return rpo_launch_status();
+}
+
+// the embedding + LayerNorm entries, as add_layernorm
+template <bool F32, bool DROP>
+int bert_embed_ln(const int* ids, const int* token_types, const int* pos, int64_t tokens, const void* word, int64_t vocab,
+                  const void* type_emb, int64_t n_types, const void* pos_emb, int64_t n_pos, const void* gamma, const void* beta,
+                  float eps, void* y, int64_t ldy, void* s, int64_t lds, bool train, int64_t d, int dtype, int drop_rc, RowDrop drop,
+                  rpo_stream_t stream) {
+    const int vec = F32 ? 4 : 8, nv = row_vectors(d, F32);
+    const int rc = first_error({row_shape(tokens, d, dtype, F32, nv),
+                                embed_tables(ids, pos, word, vocab, type_emb, n_types, pos_emb, n_pos), vec_operand(gamma),
+                                vec_operand(beta), row_operand(y, ldy, d, vec), train ? row_operand(s, lds, d, vec) : RPO_OK, drop_rc});
+    if (rc != RPO_OK || tokens == 0) return rc;
+    RPO_ROW_DISPATCH(F32, dtype, nv, bert_embed_ln_kernel, DROP, dim3((unsigned)rpo_cdiv(tokens, kRowThreads / 64)),
+                     dim3(kRowThreads), 0, (hipStream_t)stream, ids, token_types, pos, tokens, (const T*)word, vocab,
+                     (const T*)type_emb, n_types, (const T*)pos_emb, n_pos, (const T*)gamma, (const T*)beta, eps, (T*)y, ldy, (T*)s,
+                     lds, (int)d, drop);
+    return rpo_launch_status();
+}
+
+// grid of the GELU kernels: a grid-stride loop over the 16-byte vectors of rows x cols, 256 threads per block
+dim3 gelu_grid(int64_t rows, int64_t cols, int vec) {
+    const int64_t nb = rpo_cdiv(rows * (cols / vec), 256);
+    return dim3((unsigned)(nb < 8192 ? nb : 8192));
+}
+
+}  // namespace
+
+extern "C" int rpo_bidir_attn_fwd(const void* q, const void* k, const void* v, int64_t q_stride, int64_t k_stride,
+                                  int64_t v_stride, const int* cu_seqlens_q, const int* cu_seqlens_k, const int* tiles,
+                                  int64_t ntiles, int64_t tile_cols, int64_t q_block, int64_t total_q, int64_t num_heads,
+                                  int64_t num_kv_heads, int64_t head_dim, int dtype, float scale, void* out,
+                                  int64_t out_stride, float* lse, rpo_stream_t stream) {
+    return bidir_attn_fwd_launch(q, k, v, q_stride, k_stride, v_stride, cu_seqlens_q, cu_seqlens_k, tiles, ntiles, tile_cols, q_block,
+                                 total_q, num_heads, num_kv_heads, head_dim, dtype, scale, out, out_stride, lse, 0u, 1.0f, 0, stream);
 }
 
 extern "C" int rpo_add_layernorm_fwd(const void* a, int64_t lda, const void* b, int64_t ldb, const void* gamma, const void* beta,
                                      float eps, void* y, int64_t ldy, int64_t rows, int64_t d, int dtype, rpo_stream_t stream) {
-    if (!a || !gamma || !beta || !y || rows < 0 || d <= 0 || !rpo_dtype_ok(dtype) || lda < d || ldy < d || (b && ldb < d))
-        return RPO_ERR_INVALID_ARG;
-    const int nv = row_vectors(d);
-    if (dtype == RPO_DT_F32 || d % 8 || nv == 0) return RPO_ERR_UNSUPPORTED;
-    if (!rpo_aligned16(a) || (b && !rpo_aligned16(b)) || !rpo_aligned16(gamma) || !rpo_aligned16(beta) || !rpo_aligned16(y) ||
-        lda % 8 || (b && ldb % 8) || ldy % 8)
-        return RPO_ERR_UNSUPPORTED;
-    if (rows == 0) return RPO_OK;
-    const dim3 grid((unsigned)rpo_cdiv(rows, kRowThreads / 64));
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == RPO_DT_BF16)
-        RPO_ROW_DISPATCH(add_layernorm_kernel, bf16_t, nv, grid, st, (const bf16_t*)a, lda, (const bf16_t*)b, ldb,
-                         (const bf16_t*)gamma, (const bf16_t*)beta, eps, (bf16_t*)y, ldy, (bf16_t*)nullptr, (int64_t)0, rows, (int)d);
-    else
-        RPO_ROW_DISPATCH(add_layernorm_kernel, f16_t, nv, grid, st, (const f16_t*)a, lda, (const f16_t*)b, ldb,
-                         (const f16_t*)gamma, (const f16_t*)beta, eps, (f16_t*)y, ldy, (f16_t*)nullptr, (int64_t)0, rows, (int)d);
-    return rpo_launch_status();
+    return add_layernorm<false, false>(a, lda, b, ldb, gamma, beta, eps, y, ldy, nullptr, 0, false, rows, d, dtype, RPO_OK, RowDrop{},
+                                       stream);
 }
 
 extern "C" int rpo_gelu_fwd(void* x, int64_t rows, int64_t cols, int64_t ld, int dtype, rpo_stream_t stream) {
-    if (!x || rows < 0 || cols <= 0 || ld < cols || !rpo_dtype_ok(dtype)) return RPO_ERR_INVALID_ARG;
-    if (dtype == RPO_DT_F32 || cols % 8 || ld % 8 || !rpo_aligned16(x)) return RPO_ERR_UNSUPPORTED;
-    if (rows == 0) return RPO_OK;
-    const int64_t n = rows * (cols / 8), nb = rpo_cdiv(n, 256);
-    const dim3 grid((unsigned)(nb < 8192 ? nb : 8192)), block(256);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == RPO_DT_BF16) RPO_LAUNCH(gelu_kernel<bf16_t>, grid, block, 0, st, (bf16_t*)x, rows, cols, ld);
-    else RPO_LAUNCH(gelu_kernel<f16_t>, grid, block, 0, st, (f16_t*)x, rows, cols, ld);
+    const int rc = first_error({row_shape(rows, cols, dtype, false, 1), row_operand(x, ld, cols, 8)});
+    if (rc != RPO_OK || rows == 0) return rc;
+    RPO_TYPE_DISPATCH(false, dtype, gelu_kernel, gelu_grid(rows, cols, 8), dim3(256), 0, (hipStream_t)stream, (T*)x, rows, cols, ld);
     return rpo_launch_status();
 }
 
@@ -1096,41 +1305,11 @@ extern "C" int rpo_bert_embed_ln_fwd(const int* ids, const int* token_types, con
                                      int64_t vocab, const void* type_emb, int64_t n_types, const void* pos_emb, int64_t n_pos,
                                      const void* gamma, const void* beta, float eps, void* y, int64_t ldy, int64_t d, int dtype,
                                      rpo_stream_t stream) {
-    if (!ids || !pos || !word || !type_emb || !pos_emb || !gamma || !beta || !y || tokens < 0 || vocab <= 0 || n_types <= 0 ||
-        n_pos <= 0 || d <= 0 || ldy < d || !rpo_dtype_ok(dtype))
-        return RPO_ERR_INVALID_ARG;
-    const int nv = row_vectors(d);
-    if (dtype == RPO_DT_F32 || d % 8 || nv == 0 || ldy % 8) return RPO_ERR_UNSUPPORTED;
-    if (!rpo_aligned16(word) || !rpo_aligned16(type_emb) || !rpo_aligned16(pos_emb) || !rpo_aligned16(gamma) ||
-        !rpo_aligned16(beta) || !rpo_aligned16(y))
-        return RPO_ERR_UNSUPPORTED;
-    if (tokens == 0) return RPO_OK;
-    const dim3 grid((unsigned)rpo_cdiv(tokens, kRowThreads / 64));
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == RPO_DT_BF16)
-        RPO_ROW_DISPATCH(bert_embed_ln_kernel, bf16_t, nv, grid, st, ids, token_types, pos, tokens, (const bf16_t*)word, vocab,
-                         (const bf16_t*)type_emb, n_types, (const bf16_t*)pos_emb, n_pos, (const bf16_t*)gamma,
-                         (const bf16_t*)beta, eps, (bf16_t*)y, ldy, (bf16_t*)nullptr, (int64_t)0, (int)d);
-    else
-        RPO_ROW_DISPATCH(bert_embed_ln_kernel, f16_t, nv, grid, st, ids, token_types, pos, tokens, (const f16_t*)word, vocab,
-                         (const f16_t*)type_emb, n_types, (const f16_t*)pos_emb, n_pos, (const f16_t*)gamma,
-                         (const f16_t*)beta, eps, (f16_t*)y, ldy, (f16_t*)nullptr, (int64_t)0, (int)d);
-    return rpo_launch_status();
+    return bert_embed_ln<false, false>(ids, token_types, pos, tokens, word, vocab, type_emb, n_types, pos_emb, n_pos, gamma, beta, eps,
+                                       y, ldy, nullptr, 0, false, d, dtype, RPO_OK, RowDrop{}, stream);
 }
 
 // ---- f32 storage (header section 9b): entries of their own; the ones above keep answering RPO_DT_F32 with UNSUPPORTED --------
-namespace {
-int row_vectors_f32(int64_t d) {            // NV of the row kernels on 4-element vectors: 1 .. 16 (d <= 4096); 0 = too wide
-    const int64_t nv = rpo_cdiv(d, 256);
-    return nv <= 1 ? 1 : nv <= 2 ? 2 : nv <= 4 ? 4 : nv <= 8 ? 8 : nv <= 16 ? 16 : 0;
-}
-}  // namespace
-
-#define RPO_ROW_DISPATCH_F32(KERNEL, NV, GRID, ST, ...)                                                      \
-    do {                                                                                                     \
-        if (NV == 16) RPO_LAUNCH((KERNEL<float, 16>), GRID, dim3(kRowThreads), 0, ST, __VA_ARGS__);          \
-        else RPO_ROW_DISPATCH(KERNEL, float, NV, GRID, ST, __VA_ARGS__);                                     \
-    } while (0)
 
 extern "C" int rpo_bidir_attn_fwd_f32(const void* q, const void* k, const void* v, int64_t q_stride, int64_t k_stride,
                                       int64_t v_stride, const int* cu_seqlens_q, const int* cu_seqlens_k, const int* tiles,
@@ -1163,27 +1342,14 @@ extern "C" int rpo_bidir_attn_fwd_f32(const void* q, const void* k, const void* 
 extern "C" int rpo_add_layernorm_fwd_f32(const void* a, int64_t lda, const void* b, int64_t ldb, const void* gamma,
                                          const void* beta, float eps, void* y, int64_t ldy, int64_t rows, int64_t d,
                                          rpo_stream_t stream) {
-    if (!a || !gamma || !beta || !y || rows < 0 || d <= 0 || lda < d || ldy < d || (b && ldb < d)) return RPO_ERR_INVALID_ARG;
-    const int nv = row_vectors_f32(d);
-    if (d % 8 || nv == 0) return RPO_ERR_UNSUPPORTED;
-    if (!rpo_aligned16(a) || (b && !rpo_aligned16(b)) || !rpo_aligned16(gamma) || !rpo_aligned16(beta) || !rpo_aligned16(y) ||
-        lda % 4 || (b && ldb % 4) || ldy % 4)
-        return RPO_ERR_UNSUPPORTED;
-    if (rows == 0) return RPO_OK;
-    const dim3 grid((unsigned)rpo_cdiv(rows, kRowThreads / 64));
-    hipStream_t st = (hipStream_t)stream;
-    RPO_ROW_DISPATCH_F32(add_layernorm_kernel, nv, grid, st, (const float*)a, lda, (const float*)b, ldb, (const float*)gamma,
-                         (const float*)beta, eps, (float*)y, ldy, (float*)nullptr, (int64_t)0, rows, (int)d);
-    return rpo_launch_status();
+    return add_layernorm<true, false>(a, lda, b, ldb, gamma, beta, eps, y, ldy, nullptr, 0, false, rows, d, RPO_DT_F32, RPO_OK,
+                                      RowDrop{}, stream);
 }
 
 extern "C" int rpo_gelu_fwd_f32(void* x, int64_t rows, int64_t cols, int64_t ld, rpo_stream_t stream) {
-    if (!x || rows < 0 || cols <= 0 || ld < cols) return RPO_ERR_INVALID_ARG;
-    if (cols % 8 || ld % 4 || !rpo_aligned16(x)) return RPO_ERR_UNSUPPORTED;
-    if (rows == 0) return RPO_OK;
-    const int64_t n = rows * (cols / 4), nb = rpo_cdiv(n, 256);
-    const dim3 grid((unsigned)(nb < 8192 ? nb : 8192)), block(256);
-    RPO_LAUNCH(gelu_kernel<float>, grid, block, 0, (hipStream_t)stream, (float*)x, rows, cols, ld);
+    const int rc = first_error({row_shape(rows, cols, RPO_DT_F32, true, 1), row_operand(x, ld, cols, 4)});
+    if (rc != RPO_OK || rows == 0) return rc;
+    RPO_LAUNCH(gelu_kernel<float>, gelu_grid(rows, cols, 4), dim3(256), 0, (hipStream_t)stream, (float*)x, rows, cols, ld);
     return rpo_launch_status();
 }
 
@@ -1191,49 +1357,11 @@ extern "C" int rpo_bert_embed_ln_fwd_f32(const int* ids, const int* token_types,
                                          int64_t vocab, const void* type_emb, int64_t n_types, const void* pos_emb, int64_t n_pos,
                                          const void* gamma, const void* beta, float eps, void* y, int64_t ldy, int64_t d,
                                          rpo_stream_t stream) {
-    if (!ids || !pos || !word || !type_emb || !pos_emb || !gamma || !beta || !y || tokens < 0 || vocab <= 0 || n_types <= 0 ||
-        n_pos <= 0 || d <= 0 || ldy < d)
-        return RPO_ERR_INVALID_ARG;
-    const int nv = row_vectors_f32(d);
-    if (d % 8 || nv == 0 || ldy % 4) return RPO_ERR_UNSUPPORTED;
-    if (!rpo_aligned16(word) || !rpo_aligned16(type_emb) || !rpo_aligned16(pos_emb) || !rpo_aligned16(gamma) ||
-        !rpo_aligned16(beta) || !rpo_aligned16(y))
-        return RPO_ERR_UNSUPPORTED;
-    if (tokens == 0) return RPO_OK;
-    const dim3 grid((unsigned)rpo_cdiv(tokens, kRowThreads / 64));
-    hipStream_t st = (hipStream_t)stream;
-    RPO_ROW_DISPATCH_F32(bert_embed_ln_kernel, nv, grid, st, ids, token_types, pos, tokens, (const float*)word, vocab,
-                         (const float*)type_emb, n_types, (const float*)pos_emb, n_pos, (const float*)gamma, (const float*)beta, eps,
-                         (float*)y, ldy, (float*)nullptr, (int64_t)0, (int)d);
-    return rpo_launch_status();
+    return bert_embed_ln<true, false>(ids, token_types, pos, tokens, word, vocab, type_emb, n_types, pos_emb, n_pos, gamma, beta, eps,
+                                      y, ldy, nullptr, 0, false, d, RPO_DT_F32, RPO_OK, RowDrop{}, stream);
 }
 
 // ---- training entries ---------------------------------------------------------------------------------
-namespace {
-bool attn_common_ok(int64_t num_heads, int64_t num_kv_heads, int64_t head_dim, int dtype, int64_t tile_cols, int64_t block,
-                    int64_t ntiles) {
-    return !(dtype == RPO_DT_F32 || (head_dim != 32 && head_dim != 64) || num_heads != num_kv_heads || tile_cols != 2 ||
-             block != kAttnQBlock || ntiles > 0x7fffffff || num_heads > 65535);
-}
-bool dropout_args(float p_drop, unsigned* thr, float* inv_keep) {      // false: p_drop outside [0, 1)
-    if (!(p_drop >= 0.f) || !(p_drop < 1.f)) return false;
-    *thr = (unsigned)lrintf(p_drop * 65536.f);
-    *inv_keep = 1.0f / (1.0f - p_drop);
-    return true;
-}
-}  // namespace
-
-#define RPO_ATTN_DISPATCH(LAUNCH)                           \
-    do {                                                    \
-        if (dtype == RPO_DT_BF16) {                         \
-            if (head_dim == 32) LAUNCH(bf16_t, 32);         \
-            else LAUNCH(bf16_t, 64);                        \
-        } else {                                            \
-            if (head_dim == 32) LAUNCH(f16_t, 32);          \
-            else LAUNCH(f16_t, 64);                         \
-        }                                                   \
-    } while (0)
-
 extern "C" int rpo_bidir_attn_train_fwd(const void* q, const void* k, const void* v, int64_t q_stride, int64_t k_stride,
                                         int64_t v_stride, const int* cu_seqlens_q, const int* cu_seqlens_k, const int* tiles,
                                         int64_t ntiles, int64_t tile_cols, int64_t q_block, int64_t total_q, int64_t num_heads,
@@ -1241,33 +1369,10 @@ extern "C" int rpo_bidir_attn_train_fwd(const void* q, const void* k, const void
                                         uint64_t seed, void* out, int64_t out_stride, float* lse, rpo_stream_t stream) {
     unsigned thr;
     float inv_keep;
-    if (!q || !k || !v || !cu_seqlens_q || !cu_seqlens_k || !tiles || !out || !lse || ntiles < 0 || total_q <= 0 ||
-        num_heads <= 0 || num_kv_heads <= 0 || head_dim <= 0 || !rpo_dtype_ok(dtype) || q_stride <= 0 || k_stride <= 0 ||
-        v_stride <= 0 || out_stride <= 0 || !dropout_args(p_drop, &thr, &inv_keep))
-        return RPO_ERR_INVALID_ARG;
-    if (!attn_common_ok(num_heads, num_kv_heads, head_dim, dtype, tile_cols, q_block, ntiles)) return RPO_ERR_UNSUPPORTED;
-    if (!rpo_aligned16(q) || !rpo_aligned16(k) || !rpo_aligned16(v) || (reinterpret_cast<uintptr_t>(out) & 7) || q_stride % 8 ||
-        k_stride % 8 || v_stride % 8 || out_stride % 4)
-        return RPO_ERR_UNSUPPORTED;
-    if (ntiles == 0) return RPO_OK;
-    const dim3 grid((unsigned)ntiles, (unsigned)num_heads), block(64);
-    hipStream_t st = (hipStream_t)stream;
-    const float sl = scale * 1.4426950408889634f;
-    const bool drop = thr > 0;
-#define RPO_BIDIR_T(T, HD)                                                                                                       \
-    do {                                                                                                                         \
-        if (drop)                                                                                                                \
-            RPO_LAUNCH((bidir_attn_fwd_kernel<T, HD, true>), grid, block, 0, st, (const T*)q, (const T*)k, (const T*)v,          \
-                       q_stride, k_stride, v_stride, cu_seqlens_q, cu_seqlens_k, tiles, sl, (T*)out, out_stride, lse, total_q,   \
-                       thr, inv_keep, seed);                                                                                     \
-        else                                                                                                                     \
-            RPO_LAUNCH((bidir_attn_fwd_kernel<T, HD, false>), grid, block, 0, st, (const T*)q, (const T*)k, (const T*)v,         \
-                       q_stride, k_stride, v_stride, cu_seqlens_q, cu_seqlens_k, tiles, sl, (T*)out, out_stride, lse, total_q,   \
-                       0u, 1.0f, (uint64_t)0);                                                                                   \
-    } while (0)
-    RPO_ATTN_DISPATCH(RPO_BIDIR_T);
-#undef RPO_BIDIR_T
-    return rpo_launch_status();
+    if (!lse || !dropout_args(p_drop, &thr, &inv_keep)) return RPO_ERR_INVALID_ARG;
+    return bidir_attn_fwd_launch(q, k, v, q_stride, k_stride, v_stride, cu_seqlens_q, cu_seqlens_k, tiles, ntiles, tile_cols, q_block,
+                                 total_q, num_heads, num_kv_heads, head_dim, dtype, scale, out, out_stride, lse, thr, inv_keep, seed,
+                                 stream);
 }
 
 extern "C" int rpo_bidir_attn_bwd(const void* q, const void* k, const void* v, int64_t q_stride, int64_t k_stride,
@@ -1353,50 +1458,16 @@ extern "C" int rpo_bidir_attn_dropout_mask(int64_t q_row0, int64_t k_row0, int64
 extern "C" int rpo_add_layernorm_train_fwd(const void* a, int64_t lda, const void* b, int64_t ldb, const void* gamma,
                                            const void* beta, float eps, void* y, int64_t ldy, void* s, int64_t lds, int64_t rows,
                                            int64_t d, int dtype, rpo_stream_t stream) {
-    if (!a || !gamma || !beta || !y || !s || rows < 0 || d <= 0 || !rpo_dtype_ok(dtype) || lda < d || ldy < d || lds < d ||
-        (b && ldb < d))
-        return RPO_ERR_INVALID_ARG;
-    const int nv = row_vectors(d);
-    if (dtype == RPO_DT_F32 || d % 8 || nv == 0) return RPO_ERR_UNSUPPORTED;
-    if (!rpo_aligned16(a) || (b && !rpo_aligned16(b)) || !rpo_aligned16(gamma) || !rpo_aligned16(beta) || !rpo_aligned16(y) ||
-        !rpo_aligned16(s) || lda % 8 || (b && ldb % 8) || ldy % 8 || lds % 8)
-        return RPO_ERR_UNSUPPORTED;
-    if (rows == 0) return RPO_OK;
-    const dim3 grid((unsigned)rpo_cdiv(rows, kRowThreads / 64));
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == RPO_DT_BF16)
-        RPO_ROW_DISPATCH(add_layernorm_kernel, bf16_t, nv, grid, st, (const bf16_t*)a, lda, (const bf16_t*)b, ldb,
-                         (const bf16_t*)gamma, (const bf16_t*)beta, eps, (bf16_t*)y, ldy, (bf16_t*)s, lds, rows, (int)d);
-    else
-        RPO_ROW_DISPATCH(add_layernorm_kernel, f16_t, nv, grid, st, (const f16_t*)a, lda, (const f16_t*)b, ldb,
-                         (const f16_t*)gamma, (const f16_t*)beta, eps, (f16_t*)y, ldy, (f16_t*)s, lds, rows, (int)d);
-    return rpo_launch_status();
+    return add_layernorm<false, false>(a, lda, b, ldb, gamma, beta, eps, y, ldy, s, lds, true, rows, d, dtype, RPO_OK, RowDrop{},
+                                       stream);
 }
 
 extern "C" int rpo_bert_embed_ln_train_fwd(const int* ids, const int* token_types, const int* pos, int64_t tokens,
                                            const void* word, int64_t vocab, const void* type_emb, int64_t n_types,
                                            const void* pos_emb, int64_t n_pos, const void* gamma, const void* beta, float eps,
                                            void* y, int64_t ldy, void* s, int64_t lds, int64_t d, int dtype, rpo_stream_t stream) {
-    if (!ids || !pos || !word || !type_emb || !pos_emb || !gamma || !beta || !y || !s || tokens < 0 || vocab <= 0 ||
-        n_types <= 0 || n_pos <= 0 || d <= 0 || ldy < d || lds < d || !rpo_dtype_ok(dtype))
-        return RPO_ERR_INVALID_ARG;
-    const int nv = row_vectors(d);
-    if (dtype == RPO_DT_F32 || d % 8 || nv == 0 || ldy % 8 || lds % 8) return RPO_ERR_UNSUPPORTED;
-    if (!rpo_aligned16(word) || !rpo_aligned16(type_emb) || !rpo_aligned16(pos_emb) || !rpo_aligned16(gamma) ||
-        !rpo_aligned16(beta) || !rpo_aligned16(y) || !rpo_aligned16(s))
-        return RPO_ERR_UNSUPPORTED;
-    if (tokens == 0) return RPO_OK;
-    const dim3 grid((unsigned)rpo_cdiv(tokens, kRowThreads / 64));
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == RPO_DT_BF16)
-        RPO_ROW_DISPATCH(bert_embed_ln_kernel, bf16_t, nv, grid, st, ids, token_types, pos, tokens, (const bf16_t*)word, vocab,
-                         (const bf16_t*)type_emb, n_types, (const bf16_t*)pos_emb, n_pos, (const bf16_t*)gamma,
-                         (const bf16_t*)beta, eps, (bf16_t*)y, ldy, (bf16_t*)s, lds, (int)d);
-    else
-        RPO_ROW_DISPATCH(bert_embed_ln_kernel, f16_t, nv, grid, st, ids, token_types, pos, tokens, (const f16_t*)word, vocab,
-                         (const f16_t*)type_emb, n_types, (const f16_t*)pos_emb, n_pos, (const f16_t*)gamma,
-                         (const f16_t*)beta, eps, (f16_t*)y, ldy, (f16_t*)s, lds, (int)d);
-    return rpo_launch_status();
+    return bert_embed_ln<false, false>(ids, token_types, pos, tokens, word, vocab, type_emb, n_types, pos_emb, n_pos, gamma, beta, eps,
+                                       y, ldy, s, lds, true, d, dtype, RPO_OK, RowDrop{}, stream);
 }
 
 extern "C" int rpo_layernorm_bwd_blocks(int64_t rows) {
@@ -1404,324 +1475,53 @@ extern "C" int rpo_layernorm_bwd_blocks(int64_t rows) {
     return (int)(nb < kLnBwdMaxBlocks ? nb : kLnBwdMaxBlocks);
 }
 
+namespace {
+// rpo_layernorm_bwd (db = nullptr) and rpo_layernorm_drop_bwd; entry_rc = what only the one entry checks
+template <bool DROP>
+int layernorm_bwd(const void* s, int64_t lds, const void* gamma, const void* dy, int64_t lddy, float eps, void* ds, int64_t ldds,
+                  void* db, int64_t lddb, float* dgamma_partial, float* dbeta_partial, int64_t rows, int64_t d, int dtype,
+                  int entry_rc, RowDrop drop, rpo_stream_t stream) {
+    const int nv = row_vectors(d, false);
+    const int rc = first_error({row_shape(rows, d, dtype, false, nv), row_operand(s, lds, d, 8), vec_operand(gamma),
+                                row_operand(dy, lddy, d, 8), row_operand(ds, ldds, d, 8), db ? row_operand(db, lddb, d, 8) : RPO_OK,
+                                (!dgamma_partial || !dbeta_partial) ? RPO_ERR_INVALID_ARG : RPO_OK, entry_rc});
+    if (rc != RPO_OK || rows == 0) return rc;
+    const size_t red_bytes = 2 * (size_t)d * sizeof(float);     // <= 32 KiB (d <= 4096)
+    RPO_ROW_DISPATCH(false, dtype, nv, layernorm_bwd_kernel, DROP, dim3((unsigned)rpo_layernorm_bwd_blocks(rows)),
+                     dim3(64 * kLnBwdWaves), red_bytes, (hipStream_t)stream, (const T*)s, lds, (const T*)gamma, (const T*)dy, lddy, eps,
+                     (T*)ds, ldds, dgamma_partial, dbeta_partial, rows, (int)d, (T*)db, lddb, drop);
+    return rpo_launch_status();
+}
+}  // namespace
+
 extern "C" int rpo_layernorm_bwd(const void* s, int64_t lds, const void* gamma, const void* dy, int64_t lddy, float eps, void* ds,
                                  int64_t ldds, float* dgamma_partial, float* dbeta_partial, int64_t rows, int64_t d, int dtype,
                                  rpo_stream_t stream) {
-    if (!s || !gamma || !dy || !ds || !dgamma_partial || !dbeta_partial || rows <= 0 || d <= 0 || !rpo_dtype_ok(dtype) ||
-        lds < d || lddy < d || ldds < d)
-        return RPO_ERR_INVALID_ARG;
-    const int nv = row_vectors(d);
-    if (dtype == RPO_DT_F32 || d % 8 || nv == 0) return RPO_ERR_UNSUPPORTED;
-    if (!rpo_aligned16(s) || !rpo_aligned16(gamma) || !rpo_aligned16(dy) || !rpo_aligned16(ds) || lds % 8 || lddy % 8 || ldds % 8)
-        return RPO_ERR_UNSUPPORTED;
-    const dim3 grid((unsigned)rpo_layernorm_bwd_blocks(rows)), block(64 * kLnBwdWaves);
-    const size_t red_bytes = 2 * (size_t)d * sizeof(float);     // <= 32 KiB (d <= 4096)
-    hipStream_t st = (hipStream_t)stream;
-#define RPO_LN_BWD(T, NV)                                                                                                   \
-    RPO_LAUNCH((layernorm_bwd_kernel<T, NV>), grid, block, red_bytes, st, (const T*)s, lds, (const T*)gamma, (const T*)dy, lddy, eps, \
-               (T*)ds, ldds, dgamma_partial, dbeta_partial, rows, (int)d)
-#define RPO_LN_BWD_T(T)                  \
-    do {                                 \
-        if (nv == 1) RPO_LN_BWD(T, 1);   \
-        else if (nv == 2) RPO_LN_BWD(T, 2); \
-        else if (nv == 4) RPO_LN_BWD(T, 4); \
-        else RPO_LN_BWD(T, 8);           \
-    } while (0)
-    if (dtype == RPO_DT_BF16) RPO_LN_BWD_T(bf16_t);
-    else RPO_LN_BWD_T(f16_t);
-#undef RPO_LN_BWD_T
-#undef RPO_LN_BWD
-    return rpo_launch_status();
+    return layernorm_bwd<false>(s, lds, gamma, dy, lddy, eps, ds, ldds, nullptr, 0, dgamma_partial, dbeta_partial, rows, d, dtype,
+                                rows == 0 ? RPO_ERR_INVALID_ARG : RPO_OK, RowDrop{}, stream);
 }
 
 extern "C" int rpo_gelu_out_fwd(const void* u, int64_t ldu, void* h, int64_t ldh, int64_t rows, int64_t cols, int dtype,
                                 rpo_stream_t stream) {
-    if (!u || !h || rows < 0 || cols <= 0 || ldu < cols || ldh < cols || !rpo_dtype_ok(dtype)) return RPO_ERR_INVALID_ARG;
-    if (dtype == RPO_DT_F32 || cols % 8 || ldu % 8 || ldh % 8 || !rpo_aligned16(u) || !rpo_aligned16(h)) return RPO_ERR_UNSUPPORTED;
-    if (rows == 0) return RPO_OK;
-    const int64_t n = rows * (cols / 8), nb = rpo_cdiv(n, 256);
-    const dim3 grid((unsigned)(nb < 8192 ? nb : 8192)), block(256);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == RPO_DT_BF16) RPO_LAUNCH(gelu_out_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)u, ldu, (bf16_t*)h, ldh, rows, cols);
-    else RPO_LAUNCH(gelu_out_kernel<f16_t>, grid, block, 0, st, (const f16_t*)u, ldu, (f16_t*)h, ldh, rows, cols);
+    const int rc = first_error({row_shape(rows, cols, dtype, false, 1), row_operand(u, ldu, cols, 8), row_operand(h, ldh, cols, 8)});
+    if (rc != RPO_OK || rows == 0) return rc;
+    RPO_TYPE_DISPATCH(false, dtype, gelu_out_kernel, gelu_grid(rows, cols, 8), dim3(256), 0, (hipStream_t)stream, (const T*)u, ldu,
+                      (T*)h, ldh, rows, cols);
     return rpo_launch_status();
 }
 
 extern "C" int rpo_gelu_bwd(const void* u, int64_t ldu, const void* dh, int64_t lddh, void* du, int64_t lddu, int64_t rows,
                             int64_t cols, int dtype, rpo_stream_t stream) {
-    if (!u || !dh || !du || rows < 0 || cols <= 0 || ldu < cols || lddh < cols || lddu < cols || !rpo_dtype_ok(dtype))
-        return RPO_ERR_INVALID_ARG;
-    if (dtype == RPO_DT_F32 || cols % 8 || ldu % 8 || lddh % 8 || lddu % 8 || !rpo_aligned16(u) || !rpo_aligned16(dh) ||
-        !rpo_aligned16(du))
-        return RPO_ERR_UNSUPPORTED;
-    if (rows == 0) return RPO_OK;
-    const int64_t n = rows * (cols / 8), nb = rpo_cdiv(n, 256);
-    const dim3 grid((unsigned)(nb < 8192 ? nb : 8192)), block(256);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == RPO_DT_BF16)
-        RPO_LAUNCH(gelu_bwd_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)u, ldu, (const bf16_t*)dh, lddh, (bf16_t*)du, lddu, rows, cols);
-    else
-        RPO_LAUNCH(gelu_bwd_kernel<f16_t>, grid, block, 0, st, (const f16_t*)u, ldu, (const f16_t*)dh, lddh, (f16_t*)du, lddu, rows, cols);
+    const int rc = first_error({row_shape(rows, cols, dtype, false, 1), row_operand(u, ldu, cols, 8), row_operand(dh, lddh, cols, 8),
+                                row_operand(du, lddu, cols, 8)});
+    if (rc != RPO_OK || rows == 0) return rc;
+    RPO_TYPE_DISPATCH(false, dtype, gelu_bwd_kernel, gelu_grid(rows, cols, 8), dim3(256), 0, (hipStream_t)stream, (const T*)u, ldu,
+                      (const T*)dh, lddh, (T*)du, lddu, rows, cols);
     return rpo_launch_status();
 }
 
-// ---- hidden-state dropout inside the row kernels ---------------------------------------------------------
-// keep(seed, site, packed row, column): the attention dropout's stateless function with (site, row, column) in the places of
-// (head, query row, key row): key = dropout_key(seed, site), bits = dropout_bits(key, row, column >> 2), one 16-bit field per
-// column of the group of 4, KEPT when field >= thr = round(p_drop * 65536).  A lane's 16-byte vector (8 columns) takes two Philox
-// evaluations.  site 0 = the embedding output, 1 + 2 i / 2 + 2 i = the two `dropout(dense(..))` of block i; the seed is
-// ops.bert_hidden_seed(call seed), which no block's attention seed equals.  A recomputed forward (gradient checkpointing) and the
-// backward evaluate the function again: no mask is stored and no generator state is kept.
-// Rounding points are those of the unfused path, x -> round(f32(x) * inv_keep) * keep on stored values: the dense output before
-// the add (add + LayerNorm), the ROUNDED LayerNorm output (embedding), the rounded ds (backward, towards the dense output).
-// These are kernels of their own beside add_layernorm_kernel / bert_embed_ln_kernel / layernorm_bwd_kernel, which stay as they are.
-namespace {
-
-__device__ __forceinline__ bool hidden_keep(uint64_t seed, int site, int row, int col, unsigned thr) {
-    return dropout_field_keep(dropout_bits(dropout_key(seed, site), row, col >> 2), col, thr);
-}
-// t <- round(t * inv_keep) * keep for the 8 columns c0 .. c0 + 7 (c0 % 8 == 0) of one row; key = dropout_key(seed, site)
-template <typename T>
-__device__ __forceinline__ void hidden_drop8(Vec16<T>& t, unsigned key, int row, int c0, unsigned thr, float inv_keep) {
-    const DropBits lo = dropout_bits(key, row, c0 >> 2), hi = dropout_bits(key, row, (c0 >> 2) + 1);
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-        t.v[e] = Elem<T>::round(t.v[e] * inv_keep) * (dropout_field_keep(e < 4 ? lo : hi, c0 + e, thr) ? 1.f : 0.f);
-}
-
-// layernorm_store's arithmetic, the f32 results left in x (not stored)
-template <typename T, int NV>
-__device__ __forceinline__ void layernorm_rows(Vec16<T> (&x)[NV], const T* __restrict__ gamma, const T* __restrict__ beta,
-                                               float eps, int d, int lane) {
-    float sum = 0.f;
-#pragma unroll
-    for (int j = 0; j < NV; ++j)
-        if (8 * (lane + 64 * j) < d)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) sum += x[j].v[e];
-    const float mean = wave_sum(sum) / (float)d;
-    float sq = 0.f;
-#pragma unroll
-    for (int j = 0; j < NV; ++j)
-        if (8 * (lane + 64 * j) < d)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float c = x[j].v[e] - mean;
-                sq = fmaf(c, c, sq);
-            }
-    const float rstd = rsqrtf(wave_sum(sq) / (float)d + eps);
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const int c0 = 8 * (lane + 64 * j);
-        if (c0 < d) {
-            Vec16<T> gw, bw;
-            gw.load(gamma + c0);
-            bw.load(beta + c0);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) x[j].v[e] = fmaf((x[j].v[e] - mean) * rstd, gw.v[e], bw.v[e]);
-        }
-    }
-}
-
-// s = round(a + round(b * inv_keep) * keep), y = LayerNorm(s); s stored for the backward
-template <typename T, int NV>
-__global__ __launch_bounds__(kRowThreads) void add_layernorm_drop_kernel(const T* __restrict__ a, int64_t lda, const T* __restrict__ b,
-                                                                          int64_t ldb, const T* __restrict__ gamma,
-                                                                          const T* __restrict__ beta, float eps, T* __restrict__ y,
-                                                                          int64_t ldy, T* __restrict__ s_out, int64_t lds,
-                                                                          int64_t rows, int d, unsigned thr, float inv_keep,
-                                                                          uint64_t seed, int site) {
-    const int64_t row = (int64_t)blockIdx.x * (kRowThreads / 64) + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (row >= rows) return;
-    const unsigned key = dropout_key(seed, site);
-    Vec16<T> x[NV];
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const int c0 = 8 * (lane + 64 * j);
-        if (c0 < d) {
-            Vec16<T> t;
-            x[j].load(a + row * lda + c0);
-            t.load(b + row * ldb + c0);
-            hidden_drop8<T>(t, key, (int)row, c0, thr, inv_keep);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) x[j].v[e] = Elem<T>::round(x[j].v[e] + t.v[e]);
-            x[j].store(s_out + row * lds + c0);
-        }
-    }
-    layernorm_rows<T, NV>(x, gamma, beta, eps, d, lane);
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const int c0 = 8 * (lane + 64 * j);
-        if (c0 < d) x[j].store(y + row * ldy + c0);
-    }
-}
-
-// bert_embed_ln_kernel with y = round(round(LayerNorm(s)) * inv_keep) * keep
-template <typename T, int NV>
-__global__ __launch_bounds__(kRowThreads) void bert_embed_ln_drop_kernel(
-    const int* __restrict__ ids, const int* __restrict__ tts, const int* __restrict__ pos, int64_t tokens,
-    const T* __restrict__ word, int64_t vocab, const T* __restrict__ temb, int64_t ntypes, const T* __restrict__ pemb,
-    int64_t npos, const T* __restrict__ gamma, const T* __restrict__ beta, float eps, T* __restrict__ y, int64_t ldy,
-    T* __restrict__ s_out, int64_t lds, int d, unsigned thr, float inv_keep, uint64_t seed, int site) {
-    const int64_t row = (int64_t)blockIdx.x * (kRowThreads / 64) + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (row >= tokens) return;
-    const int64_t wi = clamp_index(ids[row], vocab);            // clamped into their tables, as bert_embed_ln_kernel
-    const int64_t ti = tts ? clamp_index(tts[row], ntypes) : 0;
-    const int64_t pi = clamp_index(pos[row], npos);
-    const unsigned key = dropout_key(seed, site);
-    Vec16<T> x[NV];
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const int c0 = 8 * (lane + 64 * j);
-        if (c0 < d) {
-            Vec16<T> t, p;
-            x[j].load(word + wi * d + c0);
-            t.load(temb + ti * d + c0);
-            p.load(pemb + pi * d + c0);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) x[j].v[e] = Elem<T>::round(Elem<T>::round(x[j].v[e] + t.v[e]) + p.v[e]);   // (w + t) + p
-            x[j].store(s_out + row * lds + c0);
-        }
-    }
-    layernorm_rows<T, NV>(x, gamma, beta, eps, d, lane);
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const int c0 = 8 * (lane + 64 * j);
-        if (c0 < d) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) x[j].v[e] = Elem<T>::round(x[j].v[e]);       // the LayerNorm output as it would be stored
-            hidden_drop8<T>(x[j], key, (int)row, c0, thr, inv_keep);
-            x[j].store(y + row * ldy + c0);
-        }
-    }
-}
-
-// layernorm_bwd_kernel (same rows per wave, same summation order of the dgamma / dbeta partials) with the dropout of the fused
-// forwards: site_in >= 0: dy <- round(dy * inv_keep) * keep(site_in) as it is loaded (the embedding: dropout AFTER the LayerNorm);
-// db != nullptr: db = round(round(ds) * inv_keep) * keep(site_out) beside ds (add + LayerNorm: ds to a, db to the dense output b).
-template <typename T, int NV>
-__global__ __launch_bounds__(64 * kLnBwdWaves) void layernorm_drop_bwd_kernel(
-    const T* __restrict__ s, int64_t lds, const T* __restrict__ gamma, const T* __restrict__ dy, int64_t lddy, float eps,
-    T* __restrict__ ds, int64_t ldds, T* __restrict__ db_out, int64_t lddb, float* __restrict__ dgp, float* __restrict__ dbp,
-    int64_t rows, int d, unsigned thr, float inv_keep, uint64_t seed, int site_in, int site_out) {
-    extern __shared__ float ln_red[];       // [2][d]: the block's dgamma | dbeta sums
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned key_in = dropout_key(seed, site_in), key_out = dropout_key(seed, site_out);
-    float dg[NV][8], db[NV][8];
-    Vec16<T> gw[NV];
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) dg[j][e] = db[j][e] = 0.f;
-        if (8 * (lane + 64 * j) < d) gw[j].load(gamma + 8 * (lane + 64 * j));
-    }
-    for (int64_t row = (int64_t)blockIdx.x * kLnBwdWaves + wave; row < rows; row += (int64_t)gridDim.x * kLnBwdWaves) {
-        Vec16<T> x[NV], g[NV];
-        float sum = 0.f;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int c0 = 8 * (lane + 64 * j);
-            if (c0 < d) {
-                x[j].load(s + row * lds + c0);
-                g[j].load(dy + row * lddy + c0);
-                if (site_in >= 0) hidden_drop8<T>(g[j], key_in, (int)row, c0, thr, inv_keep);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) sum += x[j].v[e];
-            }
-        }
-        const float mean = wave_sum(sum) / (float)d;
-        float sq = 0.f;
-#pragma unroll
-        for (int j = 0; j < NV; ++j)
-            if (8 * (lane + 64 * j) < d)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float c = x[j].v[e] - mean;
-                    sq = fmaf(c, c, sq);
-                }
-        const float rstd = rsqrtf(wave_sum(sq) / (float)d + eps);
-        float c1 = 0.f, c2 = 0.f;
-#pragma unroll
-        for (int j = 0; j < NV; ++j)
-            if (8 * (lane + 64 * j) < d)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float xh = (x[j].v[e] - mean) * rstd, dyv = g[j].v[e], gg = dyv * gw[j].v[e];
-                    dg[j][e] = fmaf(dyv, xh, dg[j][e]);
-                    db[j][e] += dyv;
-                    x[j].v[e] = xh;
-                    g[j].v[e] = gg;
-                    c1 += gg;
-                    c2 = fmaf(gg, xh, c2);
-                }
-        c1 = wave_sum(c1) / (float)d;
-        c2 = wave_sum(c2) / (float)d;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int c0 = 8 * (lane + 64 * j);
-            if (c0 < d) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) g[j].v[e] = rstd * (g[j].v[e] - c1 - x[j].v[e] * c2);
-                g[j].store(ds + row * ldds + c0);
-                if (db_out) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) g[j].v[e] = Elem<T>::round(g[j].v[e]);      // ds as stored
-                    hidden_drop8<T>(g[j], key_out, (int)row, c0, thr, inv_keep);
-                    g[j].store(db_out + row * lddb + c0);
-                }
-            }
-        }
-    }
-    for (int w = 0; w < kLnBwdWaves; ++w) {
-        if (wave == w) {
-#pragma unroll
-            for (int j = 0; j < NV; ++j) {
-                const int c0 = 8 * (lane + 64 * j);
-                if (c0 < d) {
-                    float* gl = ln_red + c0;
-                    float* bl = ln_red + d + c0;
-                    float* gp = dgp + (int64_t)blockIdx.x * d + c0;
-                    float* bp = dbp + (int64_t)blockIdx.x * d + c0;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const float a = w == 0 ? dg[j][e] : gl[e] + dg[j][e];
-                        const float b = w == 0 ? db[j][e] : bl[e] + db[j][e];
-                        if (w == kLnBwdWaves - 1) {
-                            gp[e] = a;
-                            bp[e] = b;
-                        } else {
-                            gl[e] = a;
-                            bl[e] = b;
-                        }
-                    }
-                }
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// the keep mask of rows row0 .. row0 + rows - 1, columns 0 .. d - 1 of one site: mask[row][column] (tests and diagnostics)
-__global__ __launch_bounds__(256) void hidden_dropout_mask_kernel(int row0, int rows, int d, int site, unsigned thr, uint64_t seed,
-                                                                  unsigned char* __restrict__ mask) {
-    const int64_t n = (int64_t)rows * d;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        mask[i] = hidden_keep(seed, site, row0 + (int)(i / d), (int)(i % d), thr) ? 1 : 0;
-}
-
-constexpr int64_t kHiddenMaxSite = 1 << 20;     // a site is a small layer index; the bound only keeps it an int
-
-// thr / inv_keep of the kernels: p_drop below 2^-17 quantises to thr = 0 = no dropout, and then nothing is scaled either
-bool hidden_dropout_args(float p_drop, unsigned* thr, float* inv_keep) {
-    if (!dropout_args(p_drop, thr, inv_keep)) return false;
-    if (*thr == 0) *inv_keep = 1.0f;
-    return true;
-}
-
-}  // namespace
-
+// ---- hidden-state dropout inside the row kernels: the entries of the DROP = true instances ----------------
+// p_drop that quantises to thr = 0 still takes the DROP = true instance, with inv_keep = 1: every element is kept and unscaled.
 extern "C" float rpo_hidden_dropout_scale(float p_drop) {
     unsigned thr;
     float inv_keep;
@@ -1731,28 +1531,9 @@ extern "C" float rpo_hidden_dropout_scale(float p_drop) {
 extern "C" int rpo_add_layernorm_drop_fwd(const void* a, int64_t lda, const void* b, int64_t ldb, const void* gamma,
                                           const void* beta, float eps, void* y, int64_t ldy, void* s, int64_t lds, int64_t rows,
                                           int64_t d, int dtype, float p_drop, uint64_t seed, int64_t site, rpo_stream_t stream) {
-    unsigned thr;
-    float inv_keep;
-    if (!a || !b || !gamma || !beta || !y || !s || rows < 0 || rows > 0x7fffffff || d <= 0 || !rpo_dtype_ok(dtype) || lda < d ||
-        ldb < d || ldy < d || lds < d || site < 0 || site > kHiddenMaxSite || !hidden_dropout_args(p_drop, &thr, &inv_keep))
-        return RPO_ERR_INVALID_ARG;
-    const int nv = row_vectors(d);
-    if (dtype == RPO_DT_F32 || d % 8 || nv == 0) return RPO_ERR_UNSUPPORTED;
-    if (!rpo_aligned16(a) || !rpo_aligned16(b) || !rpo_aligned16(gamma) || !rpo_aligned16(beta) || !rpo_aligned16(y) ||
-        !rpo_aligned16(s) || lda % 8 || ldb % 8 || ldy % 8 || lds % 8)
-        return RPO_ERR_UNSUPPORTED;
-    if (rows == 0) return RPO_OK;
-    const dim3 grid((unsigned)rpo_cdiv(rows, kRowThreads / 64));
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == RPO_DT_BF16)
-        RPO_ROW_DISPATCH(add_layernorm_drop_kernel, bf16_t, nv, grid, st, (const bf16_t*)a, lda, (const bf16_t*)b, ldb,
-                         (const bf16_t*)gamma, (const bf16_t*)beta, eps, (bf16_t*)y, ldy, (bf16_t*)s, lds, rows, (int)d, thr,
-                         inv_keep, seed, (int)site);
-    else
-        RPO_ROW_DISPATCH(add_layernorm_drop_kernel, f16_t, nv, grid, st, (const f16_t*)a, lda, (const f16_t*)b, ldb,
-                         (const f16_t*)gamma, (const f16_t*)beta, eps, (f16_t*)y, ldy, (f16_t*)s, lds, rows, (int)d, thr,
-                         inv_keep, seed, (int)site);
-    return rpo_launch_status();
+    RowDrop drop;
+    const int drop_rc = drop_args(rows, p_drop, seed, site, &drop);
+    return add_layernorm<false, true>(a, lda, b, ldb, gamma, beta, eps, y, ldy, s, lds, true, rows, d, dtype, drop_rc, drop, stream);
 }
 
 extern "C" int rpo_bert_embed_ln_drop_fwd(const int* ids, const int* token_types, const int* pos, int64_t tokens,
@@ -1760,66 +1541,22 @@ extern "C" int rpo_bert_embed_ln_drop_fwd(const int* ids, const int* token_types
                                           const void* pos_emb, int64_t n_pos, const void* gamma, const void* beta, float eps,
                                           void* y, int64_t ldy, void* s, int64_t lds, int64_t d, int dtype, float p_drop,
                                           uint64_t seed, int64_t site, rpo_stream_t stream) {
-    unsigned thr;
-    float inv_keep;
-    if (!ids || !pos || !word || !type_emb || !pos_emb || !gamma || !beta || !y || !s || tokens < 0 || tokens > 0x7fffffff ||
-        vocab <= 0 || n_types <= 0 || n_pos <= 0 || d <= 0 || ldy < d || lds < d || !rpo_dtype_ok(dtype) || site < 0 ||
-        site > kHiddenMaxSite || !hidden_dropout_args(p_drop, &thr, &inv_keep))
-        return RPO_ERR_INVALID_ARG;
-    const int nv = row_vectors(d);
-    if (dtype == RPO_DT_F32 || d % 8 || nv == 0 || ldy % 8 || lds % 8) return RPO_ERR_UNSUPPORTED;
-    if (!rpo_aligned16(word) || !rpo_aligned16(type_emb) || !rpo_aligned16(pos_emb) || !rpo_aligned16(gamma) ||
-        !rpo_aligned16(beta) || !rpo_aligned16(y) || !rpo_aligned16(s))
-        return RPO_ERR_UNSUPPORTED;
-    if (tokens == 0) return RPO_OK;
-    const dim3 grid((unsigned)rpo_cdiv(tokens, kRowThreads / 64));
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == RPO_DT_BF16)
-        RPO_ROW_DISPATCH(bert_embed_ln_drop_kernel, bf16_t, nv, grid, st, ids, token_types, pos, tokens, (const bf16_t*)word, vocab,
-                         (const bf16_t*)type_emb, n_types, (const bf16_t*)pos_emb, n_pos, (const bf16_t*)gamma,
-                         (const bf16_t*)beta, eps, (bf16_t*)y, ldy, (bf16_t*)s, lds, (int)d, thr, inv_keep, seed, (int)site);
-    else
-        RPO_ROW_DISPATCH(bert_embed_ln_drop_kernel, f16_t, nv, grid, st, ids, token_types, pos, tokens, (const f16_t*)word, vocab,
-                         (const f16_t*)type_emb, n_types, (const f16_t*)pos_emb, n_pos, (const f16_t*)gamma,
-                         (const f16_t*)beta, eps, (f16_t*)y, ldy, (f16_t*)s, lds, (int)d, thr, inv_keep, seed, (int)site);
-    return rpo_launch_status();
+    RowDrop drop;
+    const int drop_rc = drop_args(tokens, p_drop, seed, site, &drop);
+    return bert_embed_ln<false, true>(ids, token_types, pos, tokens, word, vocab, type_emb, n_types, pos_emb, n_pos, gamma, beta, eps,
+                                      y, ldy, s, lds, true, d, dtype, drop_rc, drop, stream);
 }
 
 extern "C" int rpo_layernorm_drop_bwd(const void* s, int64_t lds, const void* gamma, const void* dy, int64_t lddy, float eps,
                                       void* ds, int64_t ldds, void* db, int64_t lddb, float* dgamma_partial, float* dbeta_partial,
                                       int64_t rows, int64_t d, int dtype, float p_drop, uint64_t seed, int64_t site_in,
                                       int64_t site_out, rpo_stream_t stream) {
-    unsigned thr;
-    float inv_keep;
-    if (!s || !gamma || !dy || !ds || !dgamma_partial || !dbeta_partial || rows < 0 || rows > 0x7fffffff || d <= 0 ||
-        !rpo_dtype_ok(dtype) || lds < d || lddy < d || ldds < d || (db && lddb < d) || site_in > kHiddenMaxSite ||
-        site_out > kHiddenMaxSite || (db && site_out < 0) || !hidden_dropout_args(p_drop, &thr, &inv_keep))
-        return RPO_ERR_INVALID_ARG;
-    const int nv = row_vectors(d);
-    if (dtype == RPO_DT_F32 || d % 8 || nv == 0) return RPO_ERR_UNSUPPORTED;
-    if (!rpo_aligned16(s) || !rpo_aligned16(gamma) || !rpo_aligned16(dy) || !rpo_aligned16(ds) || (db && !rpo_aligned16(db)) ||
-        lds % 8 || lddy % 8 || ldds % 8 || (db && lddb % 8))
-        return RPO_ERR_UNSUPPORTED;
-    if (rows == 0) return RPO_OK;               // nothing is written: the caller's partials stay as they are
-    const dim3 grid((unsigned)rpo_layernorm_bwd_blocks(rows)), block(64 * kLnBwdWaves);
-    const size_t red_bytes = 2 * (size_t)d * sizeof(float);     // <= 32 KiB (d <= 4096)
-    hipStream_t st = (hipStream_t)stream;
-    const int si = site_in < 0 ? -1 : (int)site_in, so = site_out < 0 ? 0 : (int)site_out;
-#define RPO_LN_DROP_BWD(T, NV)                                                                                                \
-    RPO_LAUNCH((layernorm_drop_bwd_kernel<T, NV>), grid, block, red_bytes, st, (const T*)s, lds, (const T*)gamma, (const T*)dy,  \
-               lddy, eps, (T*)ds, ldds, (T*)db, lddb, dgamma_partial, dbeta_partial, rows, (int)d, thr, inv_keep, seed, si, so)
-#define RPO_LN_DROP_BWD_T(T)                       \
-    do {                                           \
-        if (nv == 1) RPO_LN_DROP_BWD(T, 1);        \
-        else if (nv == 2) RPO_LN_DROP_BWD(T, 2);   \
-        else if (nv == 4) RPO_LN_DROP_BWD(T, 4);   \
-        else RPO_LN_DROP_BWD(T, 8);                \
-    } while (0)
-    if (dtype == RPO_DT_BF16) RPO_LN_DROP_BWD_T(bf16_t);
-    else RPO_LN_DROP_BWD_T(f16_t);
-#undef RPO_LN_DROP_BWD_T
-#undef RPO_LN_DROP_BWD
-    return rpo_launch_status();
+    RowDrop drop;       // site = site_out (0 where there is none: unused without db), site_in < 0: dy is not dropped
+    const int drop_rc = first_error({drop_args(rows, p_drop, seed, site_out < 0 ? 0 : site_out, &drop),
+                                     (site_in > kHiddenMaxSite || (db && site_out < 0)) ? RPO_ERR_INVALID_ARG : RPO_OK});
+    drop.site_in = site_in < 0 ? -1 : (int)site_in;
+    return layernorm_bwd<true>(s, lds, gamma, dy, lddy, eps, ds, ldds, db, lddb, dgamma_partial, dbeta_partial, rows, d, dtype,
+                               drop_rc, drop, stream);      // rows == 0: nothing is written, the caller's partials stay as they are
 }
 
 extern "C" int rpo_hidden_dropout_mask(int64_t row0, int64_t rows, int64_t d, float p_drop, uint64_t seed, int64_t site,

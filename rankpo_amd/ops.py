@@ -1429,45 +1429,40 @@ def bidir_attn(a, kv, num_heads, cu_q, cu_k, q_tiles, k_tiles, scale, p_drop: fl
     return _BidirAttn.apply(a, kv, num_heads, cu_q, cu_k, q_tiles, k_tiles, scale, p_drop, seed)
 
 
-def layernorm_bwd(s, weight, dy, eps):
-    """(ds, dgamma, dbeta) of y = LayerNorm(s) * weight + bias from the stored rounded sum s [rows, d]; dgamma / dbeta f32."""
+def _layernorm_bwd(s, dy, name, launch, *outs):
+    """Shared body of the two wrappers below: `launch(lib, dy, ds, dgamma_partial, dbeta_partial)` is the entry's status with the
+    made-contiguous dy, the fresh ds and the two per-block partial buffers -> (ds, *outs, dgamma, dbeta)."""
     lib = _lib.load()
     rows, d = s.shape
     dy = dy if dy.stride(1) == 1 and dy.stride(0) % 8 == 0 and dy.data_ptr() % 16 == 0 else dy.contiguous()
     ds = torch.empty((rows, d), dtype=s.dtype, device=s.device)
     if rows == 0:
         z = torch.zeros((d,), dtype=torch.float32, device=s.device)
-        return ds, z, z.clone()
+        return (ds, *outs, z, z.clone())
     nb = lib.rpo_layernorm_bwd_blocks(rows)
     part = torch.empty((2, nb, d), dtype=torch.float32, device=s.device)
     with torch.cuda.device(s.device):
-        check(lib.rpo_layernorm_bwd(s.data_ptr(), s.stride(0), weight.data_ptr(), dy.data_ptr(), dy.stride(0), float(eps),
-                                    ds.data_ptr(), d, part[0].data_ptr(), part[1].data_ptr(), rows, d, _dt(s), _stream(s)),
-              "rpo_layernorm_bwd")
+        check(launch(lib, dy, ds, part[0], part[1]), name)
     sums = part.sum(1)
-    return ds, sums[0], sums[1]
+    return (ds, *outs, sums[0], sums[1])
+
+
+def layernorm_bwd(s, weight, dy, eps):
+    """(ds, dgamma, dbeta) of y = LayerNorm(s) * weight + bias from the stored rounded sum s [rows, d]; dgamma / dbeta f32."""
+    rows, d = s.shape
+    return _layernorm_bwd(s, dy, "rpo_layernorm_bwd", lambda lib, dy, ds, dg, db_: lib.rpo_layernorm_bwd(
+        s.data_ptr(), s.stride(0), weight.data_ptr(), dy.data_ptr(), dy.stride(0), float(eps), ds.data_ptr(), d, dg.data_ptr(),
+        db_.data_ptr(), rows, d, _dt(s), _stream(s)))
 
 
 def layernorm_drop_bwd(s, weight, dy, eps, p_drop, seed, site_in: int = -1, site_out: int = -1):
     """`layernorm_bwd` with the fused hidden dropout -> (ds, db or None, dgamma, dbeta).  site_in >= 0: dy is dropped (site_in)
     as it is loaded; site_out >= 0: db = the dropped rounded ds (site_out), the gradient of the addend that was dropped."""
-    lib = _lib.load()
     rows, d = s.shape
-    dy = dy if dy.stride(1) == 1 and dy.stride(0) % 8 == 0 and dy.data_ptr() % 16 == 0 else dy.contiguous()
-    ds = torch.empty((rows, d), dtype=s.dtype, device=s.device)
     db = torch.empty((rows, d), dtype=s.dtype, device=s.device) if site_out >= 0 else None
-    if rows == 0:
-        z = torch.zeros((d,), dtype=torch.float32, device=s.device)
-        return ds, db, z, z.clone()
-    nb = lib.rpo_layernorm_bwd_blocks(rows)
-    part = torch.empty((2, nb, d), dtype=torch.float32, device=s.device)
-    with torch.cuda.device(s.device):
-        check(lib.rpo_layernorm_drop_bwd(s.data_ptr(), s.stride(0), weight.data_ptr(), dy.data_ptr(), dy.stride(0), float(eps),
-                                         ds.data_ptr(), d, _p(db), d, part[0].data_ptr(), part[1].data_ptr(), rows, d, _dt(s),
-                                         float(p_drop), int(seed), int(site_in), int(site_out), _stream(s)),
-              "rpo_layernorm_drop_bwd")
-    sums = part.sum(1)
-    return ds, db, sums[0], sums[1]
+    return _layernorm_bwd(s, dy, "rpo_layernorm_drop_bwd", lambda lib, dy, ds, dg, db_: lib.rpo_layernorm_drop_bwd(
+        s.data_ptr(), s.stride(0), weight.data_ptr(), dy.data_ptr(), dy.stride(0), float(eps), ds.data_ptr(), d, _p(db), d,
+        dg.data_ptr(), db_.data_ptr(), rows, d, _dt(s), float(p_drop), int(seed), int(site_in), int(site_out), _stream(s)), db)
 
 
 class _AddLayerNorm(torch.autograd.Function):

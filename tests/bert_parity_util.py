@@ -157,10 +157,11 @@ CONST_VALUES = (0.0, 1.0, -2.0)
 TINY_CENTRES = (1.0, -1.0, 0.5, 2.0, -0.25)
 OFFSET_CQ, OFFSET_CK = {32: 144.0, 64: 203.0}, 4.0
 ROW_KERNEL_WIDTHS = {                         # the widths at which the GPU tests run each of the six row kernels
-    "add_layernorm_kernel": ROW_WIDTHS, "bert_embed_ln_kernel": ROW_WIDTHS, "layernorm_bwd_kernel": ROW_WIDTHS,
-    "add_layernorm_drop_kernel": DROP_WIDTHS,
-    "bert_embed_ln_drop_kernel": DROP_WIDTHS,
-    "layernorm_drop_bwd_kernel": DROP_WIDTHS,
+    "add_layernorm_kernel<DROP false>": ROW_WIDTHS, "bert_embed_ln_kernel<DROP false>": ROW_WIDTHS,
+    "layernorm_bwd_kernel<DROP false>": ROW_WIDTHS,
+    "add_layernorm_kernel<DROP true>": DROP_WIDTHS,
+    "bert_embed_ln_kernel<DROP true>": DROP_WIDTHS,
+    "layernorm_bwd_kernel<DROP true>": DROP_WIDTHS,
 }
 
 

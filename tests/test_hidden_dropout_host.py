@@ -121,3 +121,278 @@ def test_new_entry_points_are_bound():
     assert lib.rpo_add_layernorm_drop_fwd(p, 12, p, 12, p, p, 1e-5, p, 12, p, 12, 0, 12, 2, 0.1, 5, 1, None) == -2    # d % 8
     assert lib.rpo_add_layernorm_drop_fwd(p, 64, p, 64, p, p, 1e-5, p, 64, p, 64, 0, 64, 2, 0.1, 5, -1, None) == -1   # site
     assert lib.rpo_layernorm_drop_bwd(p, 8192, p, p, 8192, 1e-5, p, 8192, p, 8192, p, p, 0, 8192, 2, 0.1, 5, -1, 1, None) == -2   # d > 4096
+
+
+# ------------------------------------------------------------------------------------------------
+# status codes of the row entries and of the two attention forwards: (entry, arguments, status), recorded from the library as it
+# was before the row kernels' dropout twins were folded into templates.  0 = OK, -1 = INVALID_ARG, -2 = UNSUPPORTED.  Every call
+# returns before a launch (rows / ntiles == 0, or an argument that is refused), so the dummy pointer PTR is never dereferenced.
+# ------------------------------------------------------------------------------------------------
+PTR = 16
+ENTRY_STATUS = [
+    ("rpo_add_layernorm_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, 0, 64, 1, None), 0),  # ok, nothing to do
+    ("rpo_add_layernorm_fwd", (0, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, 0, 64, 1, None), -1),  # null a
+    ("rpo_add_layernorm_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, 0, 64, 0, 64, 1, None), -1),  # null y
+    ("rpo_add_layernorm_fwd", (PTR, 64, PTR, 64, 0, PTR, 1e-05, PTR, 64, 0, 64, 1, None), -1),  # null gamma
+    ("rpo_add_layernorm_fwd", (PTR, 64, PTR, 64, 8, PTR, 1e-05, PTR, 64, 0, 64, 1, None), -2),  # misaligned gamma
+    ("rpo_add_layernorm_fwd", (PTR, 12, PTR, 12, PTR, PTR, 1e-05, PTR, 12, 0, 12, 1, None), -2),  # d % 8
+    ("rpo_add_layernorm_fwd", (PTR, 4104, PTR, 4104, PTR, PTR, 1e-05, PTR, 4104, 0, 4104, 1, None), -2),  # d too wide
+    ("rpo_add_layernorm_fwd", (PTR, 4096, PTR, 4096, PTR, PTR, 1e-05, PTR, 4096, 0, 4096, 1, None), 0),  # d 4096
+    ("rpo_add_layernorm_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 56, 0, 64, 1, None), -1),  # stride < d
+    ("rpo_add_layernorm_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 68, 0, 64, 1, None), -2),  # misaligned stride
+    ("rpo_add_layernorm_fwd", (PTR, 64, PTR, 68, PTR, PTR, 1e-05, PTR, 64, 0, 64, 1, None), -2),  # misaligned stride of b
+    ("rpo_add_layernorm_fwd", (PTR, 64, 0, 64, PTR, PTR, 1e-05, PTR, 64, 0, 64, 1, None), 0),  # null b
+    ("rpo_add_layernorm_fwd", (PTR, 64, 0, 3, PTR, PTR, 1e-05, PTR, 64, 0, 64, 1, None), 0),  # null b, its stride unchecked
+    ("rpo_add_layernorm_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, 0, 64, 0, None), -2),  # dtype f32
+    ("rpo_add_layernorm_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, 0, 64, 2, None), 0),  # dtype f16
+    ("rpo_add_layernorm_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, 0, 64, 7, None), -1),  # bad dtype
+    ("rpo_add_layernorm_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, -1, 64, 1, None), -1),  # rows < 0
+    ("rpo_add_layernorm_train_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 0, 64, 1, None), 0),  # ok, nothing to do
+    ("rpo_add_layernorm_train_fwd", (0, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 0, 64, 1, None), -1),  # null a
+    ("rpo_add_layernorm_train_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, 0, 64, PTR, 64, 0, 64, 1, None), -1),  # null y
+    ("rpo_add_layernorm_train_fwd", (PTR, 64, PTR, 64, 0, PTR, 1e-05, PTR, 64, PTR, 64, 0, 64, 1, None), -1),  # null gamma
+    ("rpo_add_layernorm_train_fwd", (PTR, 64, PTR, 64, 8, PTR, 1e-05, PTR, 64, PTR, 64, 0, 64, 1, None), -2),  # misaligned gamma
+    ("rpo_add_layernorm_train_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, 0, 64, 0, 64, 1, None), -1),  # null s
+    ("rpo_add_layernorm_train_fwd", (PTR, 12, PTR, 12, PTR, PTR, 1e-05, PTR, 12, PTR, 12, 0, 12, 1, None), -2),  # d % 8
+    ("rpo_add_layernorm_train_fwd", (PTR, 4104, PTR, 4104, PTR, PTR, 1e-05, PTR, 4104, PTR, 4104, 0, 4104, 1, None), -2),  # d too wide
+    ("rpo_add_layernorm_train_fwd", (PTR, 4096, PTR, 4096, PTR, PTR, 1e-05, PTR, 4096, PTR, 4096, 0, 4096, 1, None), 0),  # d 4096
+    ("rpo_add_layernorm_train_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 56, PTR, 64, 0, 64, 1, None), -1),  # stride < d
+    ("rpo_add_layernorm_train_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 68, PTR, 64, 0, 64, 1, None), -2),  # misaligned stride
+    ("rpo_add_layernorm_train_fwd", (PTR, 64, PTR, 68, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 0, 64, 1, None), -2),  # misaligned stride of b
+    ("rpo_add_layernorm_train_fwd", (PTR, 64, 0, 64, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 0, 64, 1, None), 0),  # null b
+    ("rpo_add_layernorm_train_fwd", (PTR, 64, 0, 3, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 0, 64, 1, None), 0),  # null b, its stride unchecked
+    ("rpo_add_layernorm_train_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 0, 64, 0, None), -2),  # dtype f32
+    ("rpo_add_layernorm_train_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 0, 64, 2, None), 0),  # dtype f16
+    ("rpo_add_layernorm_train_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 0, 64, 7, None), -1),  # bad dtype
+    ("rpo_add_layernorm_train_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, PTR, 64, -1, 64, 1, None), -1),  # rows < 0
+    ("rpo_add_layernorm_drop_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 0, 64, 1, 0.1, 5, 1, None), 0),  # ok, nothing to do
+    ("rpo_add_layernorm_drop_fwd", (0, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 0, 64, 1, 0.1, 5, 1, None), -1),  # null a
+    ("rpo_add_layernorm_drop_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, 0, 64, PTR, 64, 0, 64, 1, 0.1, 5, 1, None), -1),  # null y
+    ("rpo_add_layernorm_drop_fwd", (PTR, 64, PTR, 64, 0, PTR, 1e-05, PTR, 64, PTR, 64, 0, 64, 1, 0.1, 5, 1, None), -1),  # null gamma
+    ("rpo_add_layernorm_drop_fwd", (PTR, 64, PTR, 64, 8, PTR, 1e-05, PTR, 64, PTR, 64, 0, 64, 1, 0.1, 5, 1, None), -2),  # misaligned gamma
+    ("rpo_add_layernorm_drop_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, 0, 64, 0, 64, 1, 0.1, 5, 1, None), -1),  # null s
+    ("rpo_add_layernorm_drop_fwd", (PTR, 12, PTR, 12, PTR, PTR, 1e-05, PTR, 12, PTR, 12, 0, 12, 1, 0.1, 5, 1, None), -2),  # d % 8
+    ("rpo_add_layernorm_drop_fwd", (PTR, 4104, PTR, 4104, PTR, PTR, 1e-05, PTR, 4104, PTR, 4104, 0, 4104, 1, 0.1, 5, 1, None), -2),  # d too wide
+    ("rpo_add_layernorm_drop_fwd", (PTR, 4096, PTR, 4096, PTR, PTR, 1e-05, PTR, 4096, PTR, 4096, 0, 4096, 1, 0.1, 5, 1, None), 0),  # d 4096
+    ("rpo_add_layernorm_drop_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 56, PTR, 64, 0, 64, 1, 0.1, 5, 1, None), -1),  # stride < d
+    ("rpo_add_layernorm_drop_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 68, PTR, 64, 0, 64, 1, 0.1, 5, 1, None), -2),  # misaligned stride
+    ("rpo_add_layernorm_drop_fwd", (PTR, 64, PTR, 68, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 0, 64, 1, 0.1, 5, 1, None), -2),  # misaligned stride of b
+    ("rpo_add_layernorm_drop_fwd", (PTR, 64, 0, 64, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 0, 64, 1, 0.1, 5, 1, None), -1),  # null b
+    ("rpo_add_layernorm_drop_fwd", (PTR, 64, 0, 3, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 0, 64, 1, 0.1, 5, 1, None), -1),  # null b, its stride unchecked
+    ("rpo_add_layernorm_drop_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 0, 64, 0, 0.1, 5, 1, None), -2),  # dtype f32
+    ("rpo_add_layernorm_drop_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 0, 64, 2, 0.1, 5, 1, None), 0),  # dtype f16
+    ("rpo_add_layernorm_drop_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 0, 64, 7, 0.1, 5, 1, None), -1),  # bad dtype
+    ("rpo_add_layernorm_drop_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, PTR, 64, -1, 64, 1, 0.1, 5, 1, None), -1),  # rows < 0
+    ("rpo_add_layernorm_drop_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 0, 64, 1, 1.0, 5, 1, None), -1),  # p_drop 1
+    ("rpo_add_layernorm_drop_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 0, 64, 1, 0.0, 5, 1, None), 0),  # p_drop 0
+    ("rpo_add_layernorm_drop_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 0, 64, 1, 0.1, 5, -1, None), -1),  # site -1
+    ("rpo_add_layernorm_drop_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 0, 64, 1, 0.1, 5, 1048577, None), -1),  # site too large
+    ("rpo_add_layernorm_drop_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 0, 64, 1, 0.1, 5, 1048576, None), 0),  # site at the bound
+    ("rpo_add_layernorm_drop_fwd", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 2147483648, 64, 1, 0.1, 5, 1, None), -1),  # rows 2^31
+    ("rpo_add_layernorm_drop_fwd", (PTR, 12, PTR, 12, PTR, PTR, 1e-05, PTR, 12, PTR, 12, 2147483648, 12, 1, 0.1, 5, 1, None), -1),  # rows 2^31, d % 8
+    ("rpo_add_layernorm_fwd_f32", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, 0, 64, None), 0),  # ok, nothing to do
+    ("rpo_add_layernorm_fwd_f32", (0, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, 0, 64, None), -1),  # null a
+    ("rpo_add_layernorm_fwd_f32", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, 0, 64, 0, 64, None), -1),  # null y
+    ("rpo_add_layernorm_fwd_f32", (PTR, 64, PTR, 64, 0, PTR, 1e-05, PTR, 64, 0, 64, None), -1),  # null gamma
+    ("rpo_add_layernorm_fwd_f32", (PTR, 64, PTR, 64, 8, PTR, 1e-05, PTR, 64, 0, 64, None), -2),  # misaligned gamma
+    ("rpo_add_layernorm_fwd_f32", (PTR, 12, PTR, 12, PTR, PTR, 1e-05, PTR, 12, 0, 12, None), -2),  # d % 8
+    ("rpo_add_layernorm_fwd_f32", (PTR, 4104, PTR, 4104, PTR, PTR, 1e-05, PTR, 4104, 0, 4104, None), -2),  # d too wide
+    ("rpo_add_layernorm_fwd_f32", (PTR, 4096, PTR, 4096, PTR, PTR, 1e-05, PTR, 4096, 0, 4096, None), 0),  # d 4096
+    ("rpo_add_layernorm_fwd_f32", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 56, 0, 64, None), -1),  # stride < d
+    ("rpo_add_layernorm_fwd_f32", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 66, 0, 64, None), -2),  # misaligned stride
+    ("rpo_add_layernorm_fwd_f32", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 68, 0, 64, None), 0),  # stride % 4 only
+    ("rpo_add_layernorm_fwd_f32", (PTR, 64, PTR, 66, PTR, PTR, 1e-05, PTR, 64, 0, 64, None), -2),  # misaligned stride of b
+    ("rpo_add_layernorm_fwd_f32", (PTR, 64, 0, 64, PTR, PTR, 1e-05, PTR, 64, 0, 64, None), 0),  # null b
+    ("rpo_add_layernorm_fwd_f32", (PTR, 64, 0, 3, PTR, PTR, 1e-05, PTR, 64, 0, 64, None), 0),  # null b, its stride unchecked
+    ("rpo_add_layernorm_fwd_f32", (PTR, 64, PTR, 64, PTR, PTR, 1e-05, PTR, 64, -1, 64, None), -1),  # rows < 0
+    ("rpo_bert_embed_ln_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, 64, 1, None), 0),  # ok, nothing to do
+    ("rpo_bert_embed_ln_fwd", (0, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, 64, 1, None), -1),  # null ids
+    ("rpo_bert_embed_ln_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, 0, 64, 64, 1, None), -1),  # null y
+    ("rpo_bert_embed_ln_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, 0, PTR, 1e-05, PTR, 64, 64, 1, None), -1),  # null gamma
+    ("rpo_bert_embed_ln_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, 8, PTR, 1e-05, PTR, 64, 64, 1, None), -2),  # misaligned gamma
+    ("rpo_bert_embed_ln_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 12, 12, 1, None), -2),  # d % 8
+    ("rpo_bert_embed_ln_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 4104, 4104, 1, None), -2),  # d too wide
+    ("rpo_bert_embed_ln_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 4096, 4096, 1, None), 0),  # d 4096
+    ("rpo_bert_embed_ln_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 56, 64, 1, None), -1),  # stride < d
+    ("rpo_bert_embed_ln_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 68, 64, 1, None), -2),  # misaligned stride
+    ("rpo_bert_embed_ln_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, 64, 0, None), -2),  # dtype f32
+    ("rpo_bert_embed_ln_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, 64, 2, None), 0),  # dtype f16
+    ("rpo_bert_embed_ln_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, 64, 7, None), -1),  # bad dtype
+    ("rpo_bert_embed_ln_fwd", (PTR, PTR, PTR, -1, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, 64, 1, None), -1),  # rows < 0
+    ("rpo_bert_embed_ln_fwd", (PTR, PTR, PTR, 0, PTR, 0, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, 64, 1, None), -1),  # vocab 0
+    ("rpo_bert_embed_ln_fwd", (PTR, 0, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, 64, 1, None), 0),  # null token types
+    ("rpo_bert_embed_ln_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, 24, 8, PTR, PTR, 1e-05, PTR, 64, 64, 1, None), -2),  # misaligned table
+    ("rpo_bert_embed_ln_train_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 64, 1, None), 0),  # ok, nothing to do
+    ("rpo_bert_embed_ln_train_fwd", (0, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 64, 1, None), -1),  # null ids
+    ("rpo_bert_embed_ln_train_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, 0, 64, PTR, 64, 64, 1, None), -1),  # null y
+    ("rpo_bert_embed_ln_train_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, 0, PTR, 1e-05, PTR, 64, PTR, 64, 64, 1, None), -1),  # null gamma
+    ("rpo_bert_embed_ln_train_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, 8, PTR, 1e-05, PTR, 64, PTR, 64, 64, 1, None), -2),  # misaligned gamma
+    ("rpo_bert_embed_ln_train_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, 0, 64, 64, 1, None), -1),  # null s
+    ("rpo_bert_embed_ln_train_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 12, PTR, 12, 12, 1, None), -2),  # d % 8
+    ("rpo_bert_embed_ln_train_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 4104, PTR, 4104, 4104, 1, None), -2),  # d too wide
+    ("rpo_bert_embed_ln_train_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 4096, PTR, 4096, 4096, 1, None), 0),  # d 4096
+    ("rpo_bert_embed_ln_train_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 56, PTR, 64, 64, 1, None), -1),  # stride < d
+    ("rpo_bert_embed_ln_train_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 68, PTR, 64, 64, 1, None), -2),  # misaligned stride
+    ("rpo_bert_embed_ln_train_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 64, 0, None), -2),  # dtype f32
+    ("rpo_bert_embed_ln_train_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 64, 2, None), 0),  # dtype f16
+    ("rpo_bert_embed_ln_train_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 64, 7, None), -1),  # bad dtype
+    ("rpo_bert_embed_ln_train_fwd", (PTR, PTR, PTR, -1, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 64, 1, None), -1),  # rows < 0
+    ("rpo_bert_embed_ln_train_fwd", (PTR, PTR, PTR, 0, PTR, 0, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 64, 1, None), -1),  # vocab 0
+    ("rpo_bert_embed_ln_train_fwd", (PTR, 0, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 64, 1, None), 0),  # null token types
+    ("rpo_bert_embed_ln_train_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, 24, 8, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 64, 1, None), -2),  # misaligned table
+    ("rpo_bert_embed_ln_drop_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 64, 1, 0.1, 5, 1, None), 0),  # ok, nothing to do
+    ("rpo_bert_embed_ln_drop_fwd", (0, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 64, 1, 0.1, 5, 1, None), -1),  # null ids
+    ("rpo_bert_embed_ln_drop_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, 0, 64, PTR, 64, 64, 1, 0.1, 5, 1, None), -1),  # null y
+    ("rpo_bert_embed_ln_drop_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, 0, PTR, 1e-05, PTR, 64, PTR, 64, 64, 1, 0.1, 5, 1, None), -1),  # null gamma
+    ("rpo_bert_embed_ln_drop_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, 8, PTR, 1e-05, PTR, 64, PTR, 64, 64, 1, 0.1, 5, 1, None), -2),  # misaligned gamma
+    ("rpo_bert_embed_ln_drop_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, 0, 64, 64, 1, 0.1, 5, 1, None), -1),  # null s
+    ("rpo_bert_embed_ln_drop_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 12, PTR, 12, 12, 1, 0.1, 5, 1, None), -2),  # d % 8
+    ("rpo_bert_embed_ln_drop_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 4104, PTR, 4104, 4104, 1, 0.1, 5, 1, None), -2),  # d too wide
+    ("rpo_bert_embed_ln_drop_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 4096, PTR, 4096, 4096, 1, 0.1, 5, 1, None), 0),  # d 4096
+    ("rpo_bert_embed_ln_drop_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 56, PTR, 64, 64, 1, 0.1, 5, 1, None), -1),  # stride < d
+    ("rpo_bert_embed_ln_drop_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 68, PTR, 64, 64, 1, 0.1, 5, 1, None), -2),  # misaligned stride
+    ("rpo_bert_embed_ln_drop_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 64, 0, 0.1, 5, 1, None), -2),  # dtype f32
+    ("rpo_bert_embed_ln_drop_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 64, 2, 0.1, 5, 1, None), 0),  # dtype f16
+    ("rpo_bert_embed_ln_drop_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 64, 7, 0.1, 5, 1, None), -1),  # bad dtype
+    ("rpo_bert_embed_ln_drop_fwd", (PTR, PTR, PTR, -1, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 64, 1, 0.1, 5, 1, None), -1),  # rows < 0
+    ("rpo_bert_embed_ln_drop_fwd", (PTR, PTR, PTR, 0, PTR, 0, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 64, 1, 0.1, 5, 1, None), -1),  # vocab 0
+    ("rpo_bert_embed_ln_drop_fwd", (PTR, 0, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 64, 1, 0.1, 5, 1, None), 0),  # null token types
+    ("rpo_bert_embed_ln_drop_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, 24, 8, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 64, 1, 0.1, 5, 1, None), -2),  # misaligned table
+    ("rpo_bert_embed_ln_drop_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 64, 1, 1.0, 5, 1, None), -1),  # p_drop 1
+    ("rpo_bert_embed_ln_drop_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 64, 1, 0.0, 5, 1, None), 0),  # p_drop 0
+    ("rpo_bert_embed_ln_drop_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 64, 1, 0.1, 5, -1, None), -1),  # site -1
+    ("rpo_bert_embed_ln_drop_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 64, 1, 0.1, 5, 1048577, None), -1),  # site too large
+    ("rpo_bert_embed_ln_drop_fwd", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 64, 1, 0.1, 5, 1048576, None), 0),  # site at the bound
+    ("rpo_bert_embed_ln_drop_fwd", (PTR, PTR, PTR, 2147483648, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, PTR, 64, 64, 1, 0.1, 5, 1, None), -1),  # rows 2^31
+    ("rpo_bert_embed_ln_drop_fwd", (PTR, PTR, PTR, 2147483648, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 12, PTR, 12, 12, 1, 0.1, 5, 1, None), -1),  # rows 2^31, d % 8
+    ("rpo_bert_embed_ln_fwd_f32", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, 64, None), 0),  # ok, nothing to do
+    ("rpo_bert_embed_ln_fwd_f32", (0, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, 64, None), -1),  # null ids
+    ("rpo_bert_embed_ln_fwd_f32", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, 0, 64, 64, None), -1),  # null y
+    ("rpo_bert_embed_ln_fwd_f32", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, 0, PTR, 1e-05, PTR, 64, 64, None), -1),  # null gamma
+    ("rpo_bert_embed_ln_fwd_f32", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, 8, PTR, 1e-05, PTR, 64, 64, None), -2),  # misaligned gamma
+    ("rpo_bert_embed_ln_fwd_f32", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 12, 12, None), -2),  # d % 8
+    ("rpo_bert_embed_ln_fwd_f32", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 4104, 4104, None), -2),  # d too wide
+    ("rpo_bert_embed_ln_fwd_f32", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 4096, 4096, None), 0),  # d 4096
+    ("rpo_bert_embed_ln_fwd_f32", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 56, 64, None), -1),  # stride < d
+    ("rpo_bert_embed_ln_fwd_f32", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 66, 64, None), -2),  # misaligned stride
+    ("rpo_bert_embed_ln_fwd_f32", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 68, 64, None), 0),  # stride % 4 only
+    ("rpo_bert_embed_ln_fwd_f32", (PTR, PTR, PTR, -1, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, 64, None), -1),  # rows < 0
+    ("rpo_bert_embed_ln_fwd_f32", (PTR, PTR, PTR, 0, PTR, 0, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, 64, None), -1),  # vocab 0
+    ("rpo_bert_embed_ln_fwd_f32", (PTR, 0, PTR, 0, PTR, 10, PTR, 2, PTR, 8, PTR, PTR, 1e-05, PTR, 64, 64, None), 0),  # null token types
+    ("rpo_bert_embed_ln_fwd_f32", (PTR, PTR, PTR, 0, PTR, 10, PTR, 2, 24, 8, PTR, PTR, 1e-05, PTR, 64, 64, None), -2),  # misaligned table
+    ("rpo_layernorm_bwd", (0, 64, PTR, PTR, 64, 1e-05, PTR, 64, PTR, PTR, 4, 64, 1, None), -1),  # null s
+    ("rpo_layernorm_bwd", (PTR, 64, 0, PTR, 64, 1e-05, PTR, 64, PTR, PTR, 4, 64, 1, None), -1),  # null gamma
+    ("rpo_layernorm_bwd", (PTR, 64, 8, PTR, 64, 1e-05, PTR, 64, PTR, PTR, 4, 64, 1, None), -2),  # misaligned gamma
+    ("rpo_layernorm_bwd", (PTR, 12, PTR, PTR, 12, 1e-05, PTR, 12, PTR, PTR, 4, 12, 1, None), -2),  # d % 8
+    ("rpo_layernorm_bwd", (PTR, 4104, PTR, PTR, 4104, 1e-05, PTR, 4104, PTR, PTR, 4, 4104, 1, None), -2),  # d too wide
+    ("rpo_layernorm_bwd", (PTR, 64, PTR, PTR, 64, 1e-05, PTR, 56, PTR, PTR, 4, 64, 1, None), -1),  # stride < d
+    ("rpo_layernorm_bwd", (PTR, 64, PTR, PTR, 64, 1e-05, PTR, 68, PTR, PTR, 4, 64, 1, None), -2),  # misaligned stride
+    ("rpo_layernorm_bwd", (PTR, 64, PTR, PTR, 64, 1e-05, PTR, 64, PTR, PTR, 4, 64, 0, None), -2),  # dtype f32
+    ("rpo_layernorm_bwd", (PTR, 64, PTR, PTR, 64, 1e-05, PTR, 64, PTR, PTR, 4, 64, 7, None), -1),  # bad dtype
+    ("rpo_layernorm_bwd", (PTR, 64, PTR, PTR, 64, 1e-05, PTR, 64, PTR, PTR, -1, 64, 1, None), -1),  # rows < 0
+    ("rpo_layernorm_bwd", (PTR, 64, PTR, PTR, 64, 1e-05, PTR, 64, PTR, PTR, 0, 64, 1, None), -1),  # rows == 0
+    ("rpo_layernorm_drop_bwd", (PTR, 64, PTR, PTR, 64, 1e-05, PTR, 64, PTR, 64, PTR, PTR, 0, 64, 1, 0.1, 5, -1, 1, None), 0),  # ok, nothing to do
+    ("rpo_layernorm_drop_bwd", (0, 64, PTR, PTR, 64, 1e-05, PTR, 64, PTR, 64, PTR, PTR, 0, 64, 1, 0.1, 5, -1, 1, None), -1),  # null s
+    ("rpo_layernorm_drop_bwd", (PTR, 64, 0, PTR, 64, 1e-05, PTR, 64, PTR, 64, PTR, PTR, 0, 64, 1, 0.1, 5, -1, 1, None), -1),  # null gamma
+    ("rpo_layernorm_drop_bwd", (PTR, 64, 8, PTR, 64, 1e-05, PTR, 64, PTR, 64, PTR, PTR, 0, 64, 1, 0.1, 5, -1, 1, None), -2),  # misaligned gamma
+    ("rpo_layernorm_drop_bwd", (PTR, 12, PTR, PTR, 12, 1e-05, PTR, 12, PTR, 12, PTR, PTR, 0, 12, 1, 0.1, 5, -1, 1, None), -2),  # d % 8
+    ("rpo_layernorm_drop_bwd", (PTR, 4104, PTR, PTR, 4104, 1e-05, PTR, 4104, PTR, 4104, PTR, PTR, 0, 4104, 1, 0.1, 5, -1, 1, None), -2),  # d too wide
+    ("rpo_layernorm_drop_bwd", (PTR, 4096, PTR, PTR, 4096, 1e-05, PTR, 4096, PTR, 4096, PTR, PTR, 0, 4096, 1, 0.1, 5, -1, 1, None), 0),  # d 4096
+    ("rpo_layernorm_drop_bwd", (PTR, 64, PTR, PTR, 64, 1e-05, PTR, 56, PTR, 64, PTR, PTR, 0, 64, 1, 0.1, 5, -1, 1, None), -1),  # stride < d
+    ("rpo_layernorm_drop_bwd", (PTR, 64, PTR, PTR, 64, 1e-05, PTR, 68, PTR, 64, PTR, PTR, 0, 64, 1, 0.1, 5, -1, 1, None), -2),  # misaligned stride
+    ("rpo_layernorm_drop_bwd", (PTR, 64, PTR, PTR, 64, 1e-05, PTR, 64, 0, 3, PTR, PTR, 0, 64, 1, 0.1, 5, -1, 1, None), 0),  # null db
+    ("rpo_layernorm_drop_bwd", (PTR, 64, PTR, PTR, 64, 1e-05, PTR, 64, 0, 64, PTR, PTR, 0, 64, 1, 0.1, 5, -1, -1, None), 0),  # null db, no site_out
+    ("rpo_layernorm_drop_bwd", (PTR, 64, PTR, PTR, 64, 1e-05, PTR, 64, PTR, 64, PTR, PTR, 0, 64, 1, 0.1, 5, -1, -1, None), -1),  # db without site_out
+    ("rpo_layernorm_drop_bwd", (PTR, 64, PTR, PTR, 64, 1e-05, PTR, 64, PTR, 64, PTR, PTR, 0, 64, 1, 0.1, 5, 1048577, 1, None), -1),  # site_in too large
+    ("rpo_layernorm_drop_bwd", (PTR, 64, PTR, PTR, 64, 1e-05, PTR, 64, PTR, 64, PTR, PTR, 0, 64, 1, 0.1, 5, 0, 1, None), 0),  # site_in set
+    ("rpo_layernorm_drop_bwd", (PTR, 64, PTR, PTR, 64, 1e-05, PTR, 64, PTR, 64, PTR, PTR, 0, 64, 0, 0.1, 5, -1, 1, None), -2),  # dtype f32
+    ("rpo_layernorm_drop_bwd", (PTR, 64, PTR, PTR, 64, 1e-05, PTR, 64, PTR, 64, PTR, PTR, 0, 64, 2, 0.1, 5, -1, 1, None), 0),  # dtype f16
+    ("rpo_layernorm_drop_bwd", (PTR, 64, PTR, PTR, 64, 1e-05, PTR, 64, PTR, 64, PTR, PTR, 0, 64, 7, 0.1, 5, -1, 1, None), -1),  # bad dtype
+    ("rpo_layernorm_drop_bwd", (PTR, 64, PTR, PTR, 64, 1e-05, PTR, 64, PTR, 64, PTR, PTR, -1, 64, 1, 0.1, 5, -1, 1, None), -1),  # rows < 0
+    ("rpo_layernorm_drop_bwd", (PTR, 64, PTR, PTR, 64, 1e-05, PTR, 64, PTR, 64, PTR, PTR, 0, 64, 1, 1.0, 5, -1, 1, None), -1),  # p_drop 1
+    ("rpo_layernorm_drop_bwd", (PTR, 64, PTR, PTR, 64, 1e-05, PTR, 64, PTR, 64, PTR, PTR, 0, 64, 1, 0.0, 5, -1, 1, None), 0),  # p_drop 0
+    ("rpo_layernorm_drop_bwd", (PTR, 64, PTR, PTR, 64, 1e-05, PTR, 64, PTR, 64, PTR, PTR, 0, 64, 1, 0.1, 5, -1, -1, None), -1),  # site -1
+    ("rpo_layernorm_drop_bwd", (PTR, 64, PTR, PTR, 64, 1e-05, PTR, 64, PTR, 64, PTR, PTR, 0, 64, 1, 0.1, 5, -1, 1048577, None), -1),  # site too large
+    ("rpo_layernorm_drop_bwd", (PTR, 64, PTR, PTR, 64, 1e-05, PTR, 64, PTR, 64, PTR, PTR, 0, 64, 1, 0.1, 5, -1, 1048576, None), 0),  # site at the bound
+    ("rpo_layernorm_drop_bwd", (PTR, 64, PTR, PTR, 64, 1e-05, PTR, 64, PTR, 64, PTR, PTR, 2147483648, 64, 1, 0.1, 5, -1, 1, None), -1),  # rows 2^31
+    ("rpo_layernorm_drop_bwd", (PTR, 12, PTR, PTR, 12, 1e-05, PTR, 12, PTR, 12, PTR, PTR, 2147483648, 12, 1, 0.1, 5, -1, 1, None), -1),  # rows 2^31, d % 8
+    ("rpo_gelu_fwd", (PTR, 0, 64, 64, 1, None), 0),  # ok, nothing to do
+    ("rpo_gelu_fwd", (0, 0, 64, 64, 1, None), -1),  # null a
+    ("rpo_gelu_fwd", (PTR, 0, 12, 12, 1, None), -2),  # d % 8
+    ("rpo_gelu_fwd", (PTR, 0, 4104, 4104, 1, None), 0),  # d too wide
+    ("rpo_gelu_fwd", (PTR, 0, 4096, 4096, 1, None), 0),  # d 4096
+    ("rpo_gelu_fwd", (PTR, 0, 64, 56, 1, None), -1),  # stride < d
+    ("rpo_gelu_fwd", (PTR, 0, 64, 68, 1, None), -2),  # misaligned stride
+    ("rpo_gelu_fwd", (PTR, 0, 64, 64, 0, None), -2),  # dtype f32
+    ("rpo_gelu_fwd", (PTR, 0, 64, 64, 2, None), 0),  # dtype f16
+    ("rpo_gelu_fwd", (PTR, 0, 64, 64, 7, None), -1),  # bad dtype
+    ("rpo_gelu_fwd", (PTR, -1, 64, 64, 1, None), -1),  # rows < 0
+    ("rpo_gelu_fwd_f32", (PTR, 0, 64, 64, None), 0),  # ok, nothing to do
+    ("rpo_gelu_fwd_f32", (0, 0, 64, 64, None), -1),  # null a
+    ("rpo_gelu_fwd_f32", (PTR, 0, 12, 12, None), -2),  # d % 8
+    ("rpo_gelu_fwd_f32", (PTR, 0, 4104, 4104, None), 0),  # d too wide
+    ("rpo_gelu_fwd_f32", (PTR, 0, 4096, 4096, None), 0),  # d 4096
+    ("rpo_gelu_fwd_f32", (PTR, 0, 64, 56, None), -1),  # stride < d
+    ("rpo_gelu_fwd_f32", (PTR, 0, 64, 66, None), -2),  # misaligned stride
+    ("rpo_gelu_fwd_f32", (PTR, 0, 64, 68, None), 0),  # stride % 4 only
+    ("rpo_gelu_fwd_f32", (PTR, -1, 64, 64, None), -1),  # rows < 0
+    ("rpo_gelu_out_fwd", (PTR, 64, PTR, 64, 0, 64, 1, None), 0),  # ok, nothing to do
+    ("rpo_gelu_out_fwd", (0, 64, PTR, 64, 0, 64, 1, None), -1),  # null a
+    ("rpo_gelu_out_fwd", (PTR, 64, 0, 64, 0, 64, 1, None), -1),  # null y
+    ("rpo_gelu_out_fwd", (PTR, 12, PTR, 12, 0, 12, 1, None), -2),  # d % 8
+    ("rpo_gelu_out_fwd", (PTR, 4104, PTR, 4104, 0, 4104, 1, None), 0),  # d too wide
+    ("rpo_gelu_out_fwd", (PTR, 4096, PTR, 4096, 0, 4096, 1, None), 0),  # d 4096
+    ("rpo_gelu_out_fwd", (PTR, 64, PTR, 56, 0, 64, 1, None), -1),  # stride < d
+    ("rpo_gelu_out_fwd", (PTR, 64, PTR, 68, 0, 64, 1, None), -2),  # misaligned stride
+    ("rpo_gelu_out_fwd", (PTR, 64, PTR, 64, 0, 64, 0, None), -2),  # dtype f32
+    ("rpo_gelu_out_fwd", (PTR, 64, PTR, 64, 0, 64, 2, None), 0),  # dtype f16
+    ("rpo_gelu_out_fwd", (PTR, 64, PTR, 64, 0, 64, 7, None), -1),  # bad dtype
+    ("rpo_gelu_out_fwd", (PTR, 64, PTR, 64, -1, 64, 1, None), -1),  # rows < 0
+    ("rpo_gelu_bwd", (PTR, 64, PTR, 64, PTR, 64, 0, 64, 1, None), 0),  # ok, nothing to do
+    ("rpo_gelu_bwd", (0, 64, PTR, 64, PTR, 64, 0, 64, 1, None), -1),  # null a
+    ("rpo_gelu_bwd", (PTR, 64, PTR, 64, 0, 64, 0, 64, 1, None), -1),  # null y
+    ("rpo_gelu_bwd", (PTR, 12, PTR, 12, PTR, 12, 0, 12, 1, None), -2),  # d % 8
+    ("rpo_gelu_bwd", (PTR, 4104, PTR, 4104, PTR, 4104, 0, 4104, 1, None), 0),  # d too wide
+    ("rpo_gelu_bwd", (PTR, 4096, PTR, 4096, PTR, 4096, 0, 4096, 1, None), 0),  # d 4096
+    ("rpo_gelu_bwd", (PTR, 64, PTR, 64, PTR, 56, 0, 64, 1, None), -1),  # stride < d
+    ("rpo_gelu_bwd", (PTR, 64, PTR, 64, PTR, 68, 0, 64, 1, None), -2),  # misaligned stride
+    ("rpo_gelu_bwd", (PTR, 64, PTR, 68, PTR, 64, 0, 64, 1, None), -2),  # misaligned stride of b
+    ("rpo_gelu_bwd", (PTR, 64, PTR, 64, PTR, 64, 0, 64, 0, None), -2),  # dtype f32
+    ("rpo_gelu_bwd", (PTR, 64, PTR, 64, PTR, 64, 0, 64, 2, None), 0),  # dtype f16
+    ("rpo_gelu_bwd", (PTR, 64, PTR, 64, PTR, 64, 0, 64, 7, None), -1),  # bad dtype
+    ("rpo_gelu_bwd", (PTR, 64, PTR, 64, PTR, 64, -1, 64, 1, None), -1),  # rows < 0
+    ("rpo_bidir_attn_fwd", (PTR, PTR, PTR, 64, 64, 64, PTR, PTR, PTR, 0, 2, 32, 8, 2, 2, 32, 1, 0.125, PTR, 64, PTR, None), 0),  # ok, nothing to do
+    ("rpo_bidir_attn_fwd", (0, PTR, PTR, 64, 64, 64, PTR, PTR, PTR, 0, 2, 32, 8, 2, 2, 32, 1, 0.125, PTR, 64, PTR, None), -1),  # null q
+    ("rpo_bidir_attn_fwd", (PTR, PTR, PTR, 64, 64, 64, PTR, PTR, PTR, 0, 2, 32, 8, 2, 2, 32, 1, 0.125, 0, 64, PTR, None), -1),  # null y
+    ("rpo_bidir_attn_fwd", (PTR, PTR, PTR, 64, 64, 64, PTR, PTR, PTR, 0, 2, 32, 8, 2, 2, 48, 1, 0.125, PTR, 64, PTR, None), -2),  # head_dim 48
+    ("rpo_bidir_attn_fwd", (PTR, PTR, PTR, 12, 64, 64, PTR, PTR, PTR, 0, 2, 32, 8, 2, 2, 32, 1, 0.125, PTR, 64, PTR, None), -2),  # misaligned stride
+    ("rpo_bidir_attn_fwd", (PTR, PTR, PTR, 64, 64, 64, PTR, PTR, PTR, 0, 2, 32, 8, 2, 2, 32, 1, 0.125, PTR, 6, PTR, None), -2),  # misaligned out stride
+    ("rpo_bidir_attn_fwd", (PTR, PTR, PTR, 64, 64, 64, PTR, PTR, PTR, 0, 2, 32, 8, 2, 2, 32, 0, 0.125, PTR, 64, PTR, None), -2),  # dtype f32
+    ("rpo_bidir_attn_fwd", (PTR, PTR, PTR, 64, 64, 64, PTR, PTR, PTR, 0, 2, 32, 8, 2, 2, 32, 7, 0.125, PTR, 64, PTR, None), -1),  # bad dtype
+    ("rpo_bidir_attn_fwd", (PTR, PTR, PTR, 64, 64, 64, PTR, PTR, PTR, 0, 2, 32, 8, 2, 2, 32, 1, 0.125, PTR, 64, 0, None), 0),  # null lse
+    ("rpo_bidir_attn_fwd", (PTR, PTR, PTR, 64, 64, 64, PTR, PTR, PTR, 0, 2, 32, 8, 2, 1, 32, 1, 0.125, PTR, 64, PTR, None), -2),  # kv heads
+    ("rpo_bidir_attn_fwd", (PTR, PTR, PTR, 64, 64, 64, PTR, PTR, PTR, -1, 2, 32, 8, 2, 2, 32, 1, 0.125, PTR, 64, PTR, None), -1),  # negative ntiles
+    ("rpo_bidir_attn_train_fwd", (PTR, PTR, PTR, 64, 64, 64, PTR, PTR, PTR, 0, 2, 32, 8, 2, 2, 32, 1, 0.125, 0.1, 5, PTR, 64, PTR, None), 0),  # ok, nothing to do
+    ("rpo_bidir_attn_train_fwd", (0, PTR, PTR, 64, 64, 64, PTR, PTR, PTR, 0, 2, 32, 8, 2, 2, 32, 1, 0.125, 0.1, 5, PTR, 64, PTR, None), -1),  # null q
+    ("rpo_bidir_attn_train_fwd", (PTR, PTR, PTR, 64, 64, 64, PTR, PTR, PTR, 0, 2, 32, 8, 2, 2, 32, 1, 0.125, 0.1, 5, 0, 64, PTR, None), -1),  # null y
+    ("rpo_bidir_attn_train_fwd", (PTR, PTR, PTR, 64, 64, 64, PTR, PTR, PTR, 0, 2, 32, 8, 2, 2, 48, 1, 0.125, 0.1, 5, PTR, 64, PTR, None), -2),  # head_dim 48
+    ("rpo_bidir_attn_train_fwd", (PTR, PTR, PTR, 12, 64, 64, PTR, PTR, PTR, 0, 2, 32, 8, 2, 2, 32, 1, 0.125, 0.1, 5, PTR, 64, PTR, None), -2),  # misaligned stride
+    ("rpo_bidir_attn_train_fwd", (PTR, PTR, PTR, 64, 64, 64, PTR, PTR, PTR, 0, 2, 32, 8, 2, 2, 32, 1, 0.125, 0.1, 5, PTR, 6, PTR, None), -2),  # misaligned out stride
+    ("rpo_bidir_attn_train_fwd", (PTR, PTR, PTR, 64, 64, 64, PTR, PTR, PTR, 0, 2, 32, 8, 2, 2, 32, 0, 0.125, 0.1, 5, PTR, 64, PTR, None), -2),  # dtype f32
+    ("rpo_bidir_attn_train_fwd", (PTR, PTR, PTR, 64, 64, 64, PTR, PTR, PTR, 0, 2, 32, 8, 2, 2, 32, 7, 0.125, 0.1, 5, PTR, 64, PTR, None), -1),  # bad dtype
+    ("rpo_bidir_attn_train_fwd", (PTR, PTR, PTR, 64, 64, 64, PTR, PTR, PTR, 0, 2, 32, 8, 2, 2, 32, 1, 0.125, 0.1, 5, PTR, 64, 0, None), -1),  # null lse
+    ("rpo_bidir_attn_train_fwd", (PTR, PTR, PTR, 64, 64, 64, PTR, PTR, PTR, 0, 2, 32, 8, 2, 1, 32, 1, 0.125, 0.1, 5, PTR, 64, PTR, None), -2),  # kv heads
+    ("rpo_bidir_attn_train_fwd", (PTR, PTR, PTR, 64, 64, 64, PTR, PTR, PTR, -1, 2, 32, 8, 2, 2, 32, 1, 0.125, 0.1, 5, PTR, 64, PTR, None), -1),  # negative ntiles
+    ("rpo_bidir_attn_train_fwd", (PTR, PTR, PTR, 64, 64, 64, PTR, PTR, PTR, 0, 2, 32, 8, 2, 2, 32, 1, 0.125, 1.0, 5, PTR, 64, PTR, None), -1),  # p_drop 1
+    ("rpo_bidir_attn_train_fwd", (PTR, PTR, PTR, 64, 64, 64, PTR, PTR, PTR, 0, 2, 32, 8, 2, 2, 32, 1, 0.125, -0.5, 5, PTR, 64, PTR, None), -1),  # p_drop < 0
+    ("rpo_bidir_attn_train_fwd", (PTR, PTR, PTR, 64, 64, 64, PTR, PTR, PTR, 0, 2, 32, 8, 2, 2, 32, 1, 0.125, 0.0, 5, PTR, 64, PTR, None), 0),  # p_drop 0
+]
+
+
+def test_row_and_attention_entries_keep_their_status_codes():
+    from rankpo_amd import _lib
+    lib = _lib.load()
+    assert len({entry for entry, _, _ in ENTRY_STATUS}) == 16           # the 14 row entries and the two attention forwards
+    for entry, args, want in ENTRY_STATUS:
+        assert want in (0, -1, -2)
+        assert getattr(lib, entry)(*args) == want, (entry, args, want)
