@@ -11,6 +11,36 @@ constexpr int kPoolThreads = 256;
 constexpr int kPoolWaves = kPoolThreads / RPO_WAVE;
 constexpr int kFillPerThread = 4;
 
+// The sum of squares behind the norm.  16-bit storage: f32 (the squares of 16-bit values are exact in f32, and the one rounding to
+// storage hides the sum's error).  f32 storage: f64.  A row with one dominating element -- an outlier 2^12 x the rest -- has
+// y = x / ||x|| just below 1 in that element, where an f32 ulp is 2^-24 relative, while every f32 add of a small square to the
+// partial sum that holds the outlier's rounds by up to half an ulp of ss: the f32 sum left that element 3 ulps off (d = 768 and
+// 2048, tests/test_gpu_pool_parity.py), where the stock F.normalize is within one.  The f64 sum is exact to f32, so the norm is
+// correctly rounded and y is within 1.5 ulps.  The kernels wait on memory; the f64 adds are not what they wait for.
+template <typename T> struct SsAcc { using type = float; };
+template <> struct SsAcc<float> { using type = double; };
+__device__ __forceinline__ float ss_sqrt(float ss) { return sqrtf(ss); }
+__device__ __forceinline__ float ss_sqrt(double ss) { return (float)sqrt(ss); }
+template <typename A>
+__device__ __forceinline__ A ss_wave_sum(A x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+// block_sum (common.hpp) over the accumulator type: the same fixed order
+template <typename A>
+__device__ __forceinline__ A ss_block_sum(A x, A* scratch) {
+    x = ss_wave_sum(x);
+    const int w = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) scratch[w] = x;
+    __syncthreads();
+    A t = 0;
+#pragma unroll
+    for (int i = 0; i < kPoolWaves; ++i) t += scratch[i];
+    return t;
+}
+
 // First index of the minimum of mask[0..L) (torch.argmin semantics: ties -> smallest index).
 __device__ __forceinline__ int block_argmin_first(const int64_t* __restrict__ m, int64_t L, int64_t* s_val,
                                                   int* s_idx) {
@@ -58,7 +88,8 @@ __global__ __launch_bounds__(kPoolThreads) void pool_normalize_fwd_kernel(
     float* __restrict__ norm_out) {
     __shared__ int64_t s_val[kPoolWaves];
     __shared__ int s_idx[kPoolWaves];
-    __shared__ float s_red[kPoolWaves];
+    using A = typename SsAcc<T>::type;
+    __shared__ A s_red[kPoolWaves];
     const int64_t n = blockIdx.x;
     int idx = 0;
     if (pool_mode == RPO_POOL_LAST) {
@@ -69,7 +100,7 @@ __global__ __launch_bounds__(kPoolThreads) void pool_normalize_fwd_kernel(
     T* o = out + n * d;
     constexpr int V = Elem<T>::kVec;
     const bool vec = (d % V == 0) && rpo_aligned16_dev(row) && rpo_aligned16_dev(o);
-    float ss = 0.f;
+    A ss = 0;
     if (vec && d <= (int64_t)kPoolThreads * V) {
         // the whole row fits one 16-byte vector per thread (d <= 2048 bf16 / 1024 f32: every encoder the reference names): ONE
         // load, the row stays in registers through the norm reduction -- one dependent memory round trip less per sample (round 5:
@@ -81,10 +112,10 @@ __global__ __launch_bounds__(kPoolThreads) void pool_normalize_fwd_kernel(
         if (c < d) x.load(row + c);
         if (normalize) {
 #pragma unroll
-            for (int k = 0; k < V; ++k) ss += x.v[k] * x.v[k];
-            ss = block_sum<kPoolWaves>(ss, s_red);
+            for (int k = 0; k < V; ++k) ss += (A)x.v[k] * (A)x.v[k];
+            ss = ss_block_sum(ss, s_red);
         }
-        const float nrm1 = sqrtf(ss);
+        const float nrm1 = ss_sqrt(ss);
         if (c < d) {
             if (normalize) {
 #pragma unroll
@@ -104,17 +135,17 @@ __global__ __launch_bounds__(kPoolThreads) void pool_normalize_fwd_kernel(
                 Vec16<T> x;
                 x.load(row + c);
 #pragma unroll
-                for (int k = 0; k < V; ++k) ss += x.v[k] * x.v[k];
+                for (int k = 0; k < V; ++k) ss += (A)x.v[k] * (A)x.v[k];
             }
         } else {
             for (int64_t c = threadIdx.x; c < d; c += kPoolThreads) {
                 float x = Elem<T>::ld(row + c);
-                ss += x * x;
+                ss += (A)x * (A)x;
             }
         }
-        ss = block_sum<kPoolWaves>(ss, s_red);
+        ss = ss_block_sum(ss, s_red);
     }
-    const float nrm = sqrtf(ss);
+    const float nrm = ss_sqrt(ss);
     if (vec) {
         for (int64_t c = (int64_t)threadIdx.x * V; c < d; c += (int64_t)kPoolThreads * V) {
             Vec16<T> x;
@@ -202,7 +233,7 @@ __global__ __launch_bounds__(kPoolThreads) void pool_normalize_fwd_wave_kernel(
     const T* row = h + n * sn + (int64_t)idx * sl;
     T* o = out + n * d;
     Vec16<T> x[NV];
-    float ss = 0.f;
+    typename SsAcc<T>::type ss = 0;
 #pragma unroll
     for (int j = 0; j < NV; ++j) {                      // NV loads in flight; vector j of lane l = elements (j * 64 + l) * V ...
         const int64_t c = ((int64_t)j * RPO_WAVE + lane) * V;
@@ -216,10 +247,10 @@ __global__ __launch_bounds__(kPoolThreads) void pool_normalize_fwd_wave_kernel(
 #pragma unroll
         for (int j = 0; j < NV; ++j)
 #pragma unroll
-            for (int k = 0; k < V; ++k) ss += x[j].v[k] * x[j].v[k];
-        ss = wave_sum(ss);
+            for (int k = 0; k < V; ++k) ss += (typename SsAcc<T>::type)x[j].v[k] * (typename SsAcc<T>::type)x[j].v[k];
+        ss = ss_wave_sum(ss);
     }
-    const float nrm = sqrtf(ss);
+    const float nrm = ss_sqrt(ss);
     const float den = fmaxf(nrm, eps);
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
