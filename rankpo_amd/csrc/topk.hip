@@ -235,6 +235,19 @@ __global__ __launch_bounds__(kFastThreads) void topk_merge_fast_kernel(const T* 
             }
         }
         if (boot) {
+            // A list still short of k winners that CARRIES candidates (a group of mostly NaN left fewer than k elements behind) is
+            // settled first: on top of them the quarter's up to 256 V appends -- the whole list in 16-bit storage -- ran over it and
+            // reselect() dropped the excess silently (tests/test_gpu_topk_parity.py, nan-flood).  The two barriers fence the counter:
+            // every thread has read the last group's `count` before, and `carried` after, anything moves it again.
+            __syncthreads();
+            const int carried = s_count;
+            __syncthreads();
+            if (carried > 0) {
+                reselect();
+                boot = tv == -INFINITY && ti == 0x7fffffffffffffffLL;
+            }
+        }
+        if (boot) {
             if (tid < 256) {
                 const int64_t c = s0 * SEG + (int64_t)tid * V;
 #pragma unroll
