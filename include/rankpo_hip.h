@@ -447,6 +447,31 @@ int rpo_bert_embed_ln_fwd_f32(const int* ids, const int* token_types, const int*
                               rpo_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * (9c) causal f32 attention of the packed Llama pass (rankpo_amd/csrc/causal_attn_f32.hip; opt-in: encoder.LLAMA_F32_ATTENTION /
+ * LlamaEncoder.f32_attention, ModelForInference(f32_attention=True)).  Forward only, for no-grad callers; no allocation, no host
+ * sync, no atomics: deterministic.
+ *
+ * rpo_causal_attn_fwd_f32: causal, grouped-query, variable-length attention over packed tokens on v_mfma_f32_16x16x4_f32, with
+ * the numerics of rpo_bidir_attn_fwd_f32 (exact f32 products, f32 accumulation, P never rounded to 16 bits, the exponent taken of
+ * ((s - m) |scale|) log2(e) with m the running maximum of the raw scores).  q: [total_q, num_heads, head_dim], k / v: [T_k,
+ * num_kv_heads, head_dim], token strides in floats, heads contiguous (column blocks of the fused q|k|v or k|v projection output);
+ * out: [total_q, num_heads * head_dim] with token stride out_stride.  Query head h reads kv head h / (num_heads / num_kv_heads).
+ * cu_seqlens_q / cu_seqlens_k: int32 [num_seqs + 1]; query i of a sequence with lq queries and lk keys sees key j iff
+ * j <= i + (lk - lq) (bottom-right aligned: lq == lk is causal self-attention, lq == 1 is one query over every key).  lq <= lk
+ * is the caller's precondition; rows of a sequence that breaks it come out as zeros with lse = -inf where they see no key.
+ * tiles: int32 [ntiles][2] = (sequence id, first query row inside the sequence), 32 query rows per entry, the format of
+ * rpo_bidir_attn_fwd_f32; one block per (entry, kv head), one wave per query head of the group, K / V steps shared through LDS;
+ * key steps past an entry's last visible key are not executed.  lse (may be NULL): f32 [num_heads][total_q], natural log,
+ * total_q = cu_seqlens_q[num_seqs] as the kernel reads it.  head_dim 64 or 128; num_heads / num_kv_heads in {1, 2, 4, 8};
+ * tile_cols == 2, q_block == 32 (anything else: RPO_ERR_UNSUPPORTED); q / k / v / out 16-byte aligned with strides % 4 == 0.
+ * ntiles == 0 is RPO_OK and launches nothing.
+ * --------------------------------------------------------------------------------------------- */
+int rpo_causal_attn_fwd_f32(const void* q, const void* k, const void* v, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                            const int* cu_seqlens_q, const int* cu_seqlens_k, const int* tiles, int64_t ntiles,
+                            int64_t tile_cols, int64_t q_block, int64_t num_seqs, int64_t num_heads, int64_t num_kv_heads,
+                            int64_t head_dim, float scale, void* out, int64_t out_stride, float* lse, rpo_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * (10) packed TRAINING step of the BERT / XLM-R block (rankpo_amd/csrc/bert_ops.hip; BertEncoder.pooled_cls_train, used by
  * ModelForTraining.embed for CLS-pooled models).  bf16 or fp16 storage (RPO_DT_F32 is RPO_ERR_UNSUPPORTED), f32 arithmetic,
  * no allocation, no host sync, no atomics: deterministic.  Shapes, strides, work lists and alignment as in section (9) unless

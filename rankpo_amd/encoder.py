@@ -193,6 +193,11 @@ CKPT_SINGLE_INPUT = True  # a CHECKPOINTED block receives the residual stream as
 #                           tokens x 4096 x 2 bytes), which the plan spends on un-checkpointed blocks.  (HF forms the sum in bf16 and
 #                           normalises the rounded sum: this is the reference's own arithmetic; the fused kernel normalises the
 #                           unrounded f32 sum.)  False: rounds 2-4 (the A/B arm of `bench.py --ckpt-inputs 2`)
+LLAMA_F32_ATTENTION = False  # True: a float32 LlamaEncoder runs the attention of its packed no-grad pass (ModelForInference.encode,
+#                              the RankPO ref_model, eval-mode scoring) on `ops.causal_attn_f32` (causal_attn_f32.hip: causal GQA
+#                              varlen forward on the f32-input MFMA, one launch per block) instead of one SDPA call per sequence.
+#                              `LlamaEncoder.f32_attention` / ModelForInference(f32_attention=True) is the same switch for one
+#                              model.  Forward only: under grad mode, on 16-bit storage or on the CPU nothing changes.
 FWD128_ONE_WAVE = True   # head_dim 128 with 4 (8, ..) q heads per kv head: the forward walks its own list (64 queries x 4 heads per entry)
 #                          with the one-wave-per-SIMD kernel (ops.FWD_ONE_WAVE_HEAD_DIMS names the head dims); False: the 128-query kernel
 #                          of rounds 3-4 (the A/B arm of `bench.py --fwd128 classic`)
@@ -208,10 +213,13 @@ def _checkpoint_contexts():
 class VarlenCtx:
     """cu_seqlens (int32, device), the host copy of the lengths and the longest length of a packed batch; the attention kernels'
     work lists: `tiles` (128 queries per entry: forward and dQ), `k_tiles` (dK/dV), `fwd_tiles` (the forward's own list where it has
-    one -- head_dim 128: 64 queries x 4 q heads per entry, `ops.attn_fwd_tile_table` -- else None)."""
+    one -- head_dim 128: 64 queries x 4 q heads per entry, `ops.attn_fwd_tile_table` -- else None); the work lists of
+    `ops.causal_attn_f32` where the f32 attention was opted in (else None): `f32_tiles` for the full blocks (lens, lens) and
+    `f32_last_tiles` for the last block's one query per sequence ([1] * N, lens)."""
 
-    def __init__(self, cu, lens, max_len, tiles=None, k_tiles=None, fwd_tiles=None):
+    def __init__(self, cu, lens, max_len, tiles=None, k_tiles=None, fwd_tiles=None, f32_tiles=None, f32_last_tiles=None):
         self.cu, self.lens, self.max_len, self.tiles, self.k_tiles, self.fwd_tiles = cu, lens, max_len, tiles, k_tiles, fwd_tiles
+        self.f32_tiles, self.f32_last_tiles = f32_tiles, f32_last_tiles
 
 
 def _varlen_causal_attention(q, k, v, ctx: VarlenCtx):
@@ -226,6 +234,9 @@ def _varlen_causal_attention(q, k, v, ctx: VarlenCtx):
     if q.is_cuda and q.dtype in (torch.bfloat16, torch.float16):
         return torch.ops.aten._flash_attention_forward(q, k, v, ctx.cu, ctx.cu, ctx.max_len, ctx.max_len, 0.0, True,
                                                        False)[0]
+    if ctx.f32_tiles is not None and not torch.is_grad_enabled() and _ops.causal_attn_f32_ok(q, k, v):
+        # f32 storage, opted in (LLAMA_F32_ATTENTION / f32_attention), no-grad: one launch of the f32-MFMA kernel for the batch
+        return _ops.causal_attn_f32(q, k, v, ctx.cu, ctx.cu, ctx.f32_tiles, 1.0 / math.sqrt(q.shape[-1]))[0].view(q.shape)
     outs, o0 = [], 0                      # f32 or CPU (tests, config 1): one SDPA call per sequence
     for n in ctx.lens:
         a = F.scaled_dot_product_attention(q[o0:o0 + n].transpose(0, 1)[None], k[o0:o0 + n].transpose(0, 1)[None],
@@ -243,6 +254,10 @@ def _varlen_last_query_attention(q, k, v, ctx: VarlenCtx):
     if q.is_cuda and q.dtype in (torch.bfloat16, torch.float16):
         cu_q = torch.arange(N + 1, device=q.device, dtype=torch.int32)
         return torch.ops.aten._flash_attention_forward(q, k, v, cu_q, ctx.cu, 1, ctx.max_len, 0.0, False, False)[0]
+    if ctx.f32_last_tiles is not None and not torch.is_grad_enabled() and _ops.causal_attn_f32_ok(q, k, v):
+        # the same kernel with one query per sequence: bottom-right aligned, so that query sees every key
+        cu_q = torch.arange(N + 1, device=q.device, dtype=torch.int32)
+        return _ops.causal_attn_f32(q, k, v, cu_q, ctx.cu, ctx.f32_last_tiles, 1.0 / math.sqrt(q.shape[-1]))[0].view(q.shape)
     outs, o0 = [], 0
     for i, n in enumerate(ctx.lens):
         a = F.scaled_dot_product_attention(q[i:i + 1].transpose(0, 1)[None], k[o0:o0 + n].transpose(0, 1)[None],
@@ -477,6 +492,7 @@ class LlamaEncoder(nn.Module):
         self.pack_fill = True              # packed path: round the token count up to a multiple of 256 with a filler sequence
         self.hand_attention = True         # False: PyTorch's own flash-attention ops both ways (the "stock flash" control of
         #                                    bench.step_parity; a Python attribute, not an environment switch)
+        self.f32_attention = False         # True: as LLAMA_F32_ATTENTION, for this model (float32 storage, no-grad packed pass)
         self.apply(self._init)
 
     def _init(self, m):
@@ -670,7 +686,14 @@ class LlamaEncoder(nn.Module):
                 k_tiles = _ops.attn_key_tile_table(
                     lens, x.device, self.config.num_key_value_heads,
                     _ops.ATTN_KEY_BLOCK if self.config.head_dim == 64 else _ops.ATTN_KEY_BLOCK_HD128)
-        ctx = VarlenCtx(cu, lens, max(lens), tiles, k_tiles, fwd_tiles)
+        f32_tiles = f32_last_tiles = None
+        if ((LLAMA_F32_ATTENTION or self.f32_attention) and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled()
+                and _ops.causal_attn_f32_shape_ok(self.config.num_attention_heads, self.config.num_key_value_heads,
+                                                  self.config.head_dim)):
+            # opted in: the work lists of ops.causal_attn_f32 from the host lengths, uploaded asynchronously
+            f32_tiles = _ops.causal_attn_f32_tile_table(lens, lens, x.device)
+            f32_last_tiles = _ops.causal_attn_f32_tile_table([1] * N, lens, x.device)
+        ctx = VarlenCtx(cu, lens, max(lens), tiles, k_tiles, fwd_tiles, f32_tiles, f32_last_tiles)
         last_idx = (cu[1:] - 1).to(torch.int64)
         # the plan's token count is the PADDED one (every row at its batch's full width): what the collator can hand over at worst
         tok_pad = sum(m.shape[0] * m.shape[1] for _, m in batches)

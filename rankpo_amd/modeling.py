@@ -247,9 +247,14 @@ class ModelForInference(nn.Module):
         config=None,
         tokenizer=None,
         packed_f32: bool = False,
+        f32_attention: bool = False,
     ) -> None:
         """packed_f32: a float32 BERT-family encoder (neither use_fp16 nor use_bf16) runs `encode()` on the packed f32 forward
-        (`BertEncoder.native_f32`) instead of the padded PyTorch path; off by default, ignored for Llama and 16-bit models."""
+        (`BertEncoder.native_f32`) instead of the padded PyTorch path; off by default, BERT family only: ignored for Llama (see
+        f32_attention) and 16-bit models.
+        f32_attention: a float32 Llama encoder runs the attention of its packed `encode()` pass on the hand-written f32-MFMA
+        kernel (`LlamaEncoder.f32_attention`, `ops.causal_attn_f32`: one launch per block) instead of one SDPA call per sequence;
+        off by default, ignored for the BERT family and 16-bit models."""
         super().__init__()
         if use_bf16 and use_fp16:                                     # modeling.py:443-444
             raise ValueError("Cannot use fp16 and bf16 in the same time!")
@@ -277,6 +282,8 @@ class ModelForInference(nn.Module):
         self.model = self.model.to(self.device)
         if packed_f32 and hasattr(self.model, "native_f32"):
             self.model.native_f32 = True
+        if f32_attention and hasattr(self.model, "f32_attention"):
+            self.model.f32_attention = True
 
     @torch.inference_mode()
     def encode(

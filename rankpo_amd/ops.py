@@ -1225,6 +1225,83 @@ def bidir_attn_fwd(q, k, v, cu_q, cu_k, tiles, scale, want_lse: bool = False):
     return out, lse
 
 
+# ------------------------------------------------------------------------------------------------
+# (9c) causal f32 attention of the packed Llama pass (LlamaEncoder.pooled_last_token_multi under no-grad, opt-in; no autograd:
+# forward only).  Header section (9c), rankpo_amd/csrc/causal_attn_f32.hip.
+# ------------------------------------------------------------------------------------------------
+CAUSAL_ATTN_F32_Q_BLOCK = 32             # query rows per work-list entry (the only format the kernel takes)
+CAUSAL_ATTN_F32_HEAD_DIMS = (64, 128)
+CAUSAL_ATTN_F32_GROUPS = (1, 2, 4, 8)    # query heads per kv head
+
+
+def causal_attn_f32_tile_list(lens_q, lens_k):
+    """The work list of `causal_attn_f32` as a host numpy int32 [n, 2] = (sequence id, first query row): one entry per (sequence,
+    block of 32 queries).  Query i of a sequence sees the keys j <= i + (lk - lq), and an entry runs until the last visible key of
+    its last query: the entries whose last visible key lies furthest, the longest-running ones, come first.  lens_q[n] > lens_k[n]
+    (a query in front of every key) raises ValueError."""
+    import numpy as np
+    qb = CAUSAL_ATTN_F32_Q_BLOCK
+    lq = np.asarray(lens_q, dtype=np.int64).reshape(-1)
+    lk = np.asarray(lens_k, dtype=np.int64).reshape(-1)
+    if lq.shape != lk.shape:
+        raise ValueError("causal_attn_f32_tile_list: one query length and one key length per sequence")
+    if (lq > lk).any() or (lq < 0).any():
+        raise ValueError("causal_attn_f32_tile_list: 0 <= lens_q[n] <= lens_k[n] is required (bottom-right aligned causal mask)")
+    nt = (lq + qb - 1) // qb
+    seq = np.repeat(np.arange(len(lq)), nt)
+    q0 = (np.arange(int(nt.sum())) - np.repeat(np.cumsum(nt) - nt, nt)) * qb
+    last_key = np.minimum(q0 + qb, lq[seq]) - 1 + (lk - lq)[seq]
+    order = np.argsort(-last_key, kind="stable")
+    return np.stack([seq[order], q0[order]], 1).astype(np.int32).reshape(-1, 2)
+
+
+def causal_attn_f32_tile_table(lens_q, lens_k, device):
+    """`causal_attn_f32_tile_list` on the device: a pinned, asynchronous upload (nothing waits for it on the host)."""
+    t = torch.from_numpy(causal_attn_f32_tile_list(lens_q, lens_k))
+    if torch.device(device).type == "cuda":
+        t = t.pin_memory()
+    return t.to(device, non_blocking=True)
+
+
+def causal_attn_f32_shape_ok(num_heads: int, num_kv_heads: int, head_dim: int) -> bool:
+    return (head_dim in CAUSAL_ATTN_F32_HEAD_DIMS and num_kv_heads > 0 and num_heads % num_kv_heads == 0
+            and num_heads // num_kv_heads in CAUSAL_ATTN_F32_GROUPS)
+
+
+def causal_attn_f32_ok(q, k, v) -> bool:
+    """What rpo_causal_attn_fwd_f32 takes, restated: float32 on a HIP device, q [Tq, nh, hd] and k / v [Tk, nkv, hd] with heads
+    contiguous inside a token row, head_dim 64 or 128, nh / nkv in (1, 2, 4, 8), 16-byte aligned with token strides % 4 == 0."""
+    if not all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 for t in (q, k, v)):
+        return False
+    hd = q.shape[2]
+    if k.shape != v.shape or k.shape[2] != hd or not causal_attn_f32_shape_ok(q.shape[1], k.shape[1], hd):
+        return False
+    return all(t.stride(2) == 1 and t.stride(1) == hd and t.stride(0) % 4 == 0 and t.stride(0) > 0 and t.data_ptr() % 16 == 0
+               for t in (q, k, v))
+
+
+def causal_attn_f32(q, k, v, cu_q, cu_k, tiles, scale, want_lse: bool = False):
+    """Causal grouped-query variable-length attention on f32 storage: q [Tq, nh, hd], k / v [Tk, nkv, hd] (heads contiguous, token
+    stride free: column blocks of one fused projection output), cu_q / cu_k int32 [N + 1] on the device, tiles from
+    `causal_attn_f32_tile_table(lens_q, lens_k)` (which checks lens_q <= lens_k).  Query i of sequence n sees its keys
+    j <= i + (lk - lq).  Returns (out [Tq, nh * hd], lse f32 [nh, Tq] or None).  Forward only: no autograd node."""
+    if not causal_attn_f32_ok(q, k, v):
+        raise ValueError("causal_attn_f32: float32 HIP tensors [T, heads, head_dim] with head_dim in (64, 128), 1 / 2 / 4 / 8 query "
+                         "heads per kv head, heads contiguous, 16-byte aligned, token strides % 4 == 0")
+    if cu_q.numel() != cu_k.numel() or cu_q.dtype != torch.int32 or cu_k.dtype != torch.int32 or tiles.dtype != torch.int32:
+        raise ValueError("causal_attn_f32: cu_q / cu_k int32 [N + 1], tiles int32 [n, 2]")
+    lib = _lib.load()
+    Tq, nh, hd = q.shape
+    out = torch.empty((Tq, nh * hd), dtype=q.dtype, device=q.device)
+    lse = torch.empty((nh, Tq), dtype=torch.float32, device=q.device) if want_lse else None
+    with torch.cuda.device(q.device):
+        check(lib.rpo_causal_attn_fwd_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(0), k.stride(0), v.stride(0),
+                                          cu_q.data_ptr(), cu_k.data_ptr(), tiles.data_ptr(), tiles.shape[0], tiles.shape[1],
+                                          CAUSAL_ATTN_F32_Q_BLOCK, cu_q.numel() - 1, nh, k.shape[1], hd, float(scale),
+                                          out.data_ptr(), nh * hd, _p(lse), _stream(q)), "rpo_causal_attn_fwd_f32")
+    return out, lse
+
+
 def add_layernorm(a, b, weight, bias, eps, out=None):
     """LayerNorm(a + b) * weight + bias over the last dim of 2-D row-strided a / b (b may be None); a + b rounded to the storage
     dtype first.  out: [rows, d] (row stride free) or None (a new contiguous tensor)."""
