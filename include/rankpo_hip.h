@@ -472,6 +472,39 @@ int rpo_causal_attn_fwd_f32(const void* q, const void* k, const void* v, int64_t
                             int64_t head_dim, float scale, void* out, int64_t out_stride, float* lse, rpo_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * (9d) backward of the causal f32 attention of (9c), for the packed f32 Llama TRAINING pass
+ * (rankpo_amd/csrc/causal_attn_f32_bwd.hip; opt-in: encoder.LLAMA_F32_ATTENTION_TRAIN / LlamaEncoder.f32_attention_train,
+ * ModelForTraining(f32_attention=True)).  No allocation, no host sync, no atomics: deterministic.
+ *
+ * rpo_causal_attn_bwd_f32: ONE entry that launches the dQ kernel, then the dK/dV kernel, on the caller's stream, both on
+ * v_mfma_f32_16x16x4_f32 (exact f32 products, f32 accumulation, P and dS never rounded to 16 bits).  q / k / v / cu_seqlens_q /
+ * cu_seqlens_k / tiles / scale and the visibility rule j <= i + (lk - lq) as in (9c); out: [total_q, num_heads * head_dim], the
+ * forward's result, dout: its gradient, lse: f32 [num_heads][total_q], the forward's (required); all token strides in floats,
+ * heads contiguous.  k_tiles: int32 [nktiles][2] = (sequence id, first key row inside the sequence), 32 keys per entry (the
+ * format of tiles; tile_cols and q_block describe both lists), one entry per 32-key block of every sequence with keys.
+ * dq: [total_q, num_heads, head_dim], dk / dv: [T_k, num_kv_heads, head_dim], each with its own token stride (the three may be
+ * column blocks of one [T, (num_heads + 2 num_kv_heads) head_dim] buffer).  ws: f32 workspace of 2 * num_heads * total_q
+ * floats, required, 16-byte aligned: the dQ kernel leaves (delta = dout . out, 1 / L') per head and query there for the dK/dV
+ * kernel, L' the sum of exp(s scale - lse) over the query's visible keys, by which both kernels normalise the probabilities (the
+ * rounding of a single-f32 lse cancels; the exponent is taken as in (9c), log2(e) as hi + lo).
+ * Summation order: dq[i] sums the keys in ascending order (32-key steps, inside a step by the MFMA's k order); dk[j] / dv[j] sum
+ * the query steps of 32 in ascending order from the first query that sees the first key of j's 32-key entry and, inside a
+ * step, the query heads of the group in ascending order: ONE chain per element, fixed by the indices alone, so the result is
+ * deterministic and depends neither on block scheduling nor on what else is packed in the batch.
+ * Zero fill: every dq row of a listed entry and every dk / dv row of a listed key entry is written; keys no query sees (lq == 0)
+ * get exact zeros; a query whose lse is -inf contributes exact zeros, never NaN.  No access leaves a sequence.
+ * head_dim 64 or 128; num_heads / num_kv_heads in {1, 2, 4, 8}; tile_cols == 2, q_block == 32 (anything else:
+ * RPO_ERR_UNSUPPORTED before any launch); q / k / v / out / dout / dq / dk / dv / ws 16-byte aligned with strides % 4 == 0.
+ * ntiles == 0 and nktiles == 0 is RPO_OK and launches nothing; an empty list alone skips its kernel.
+ * --------------------------------------------------------------------------------------------- */
+int rpo_causal_attn_bwd_f32(const void* q, const void* k, const void* v, const void* out, const void* dout, int64_t q_stride,
+                            int64_t k_stride, int64_t v_stride, int64_t out_stride, int64_t dout_stride, const float* lse,
+                            const int* cu_seqlens_q, const int* cu_seqlens_k, const int* tiles, int64_t ntiles, const int* k_tiles,
+                            int64_t nktiles, int64_t tile_cols, int64_t q_block, int64_t num_seqs, int64_t num_heads,
+                            int64_t num_kv_heads, int64_t head_dim, float scale, void* dq, int64_t dq_stride, void* dk,
+                            int64_t dk_stride, void* dv, int64_t dv_stride, float* ws, rpo_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * (10) packed TRAINING step of the BERT / XLM-R block (rankpo_amd/csrc/bert_ops.hip; BertEncoder.pooled_cls_train, used by
  * ModelForTraining.embed for CLS-pooled models).  bf16 or fp16 storage (RPO_DT_F32 is RPO_ERR_UNSUPPORTED), f32 arithmetic,
  * no allocation, no host sync, no atomics: deterministic.  Shapes, strides, work lists and alignment as in section (9) unless

@@ -198,6 +198,13 @@ LLAMA_F32_ATTENTION = False  # True: a float32 LlamaEncoder runs the attention o
 #                              varlen forward on the f32-input MFMA, one launch per block) instead of one SDPA call per sequence.
 #                              `LlamaEncoder.f32_attention` / ModelForInference(f32_attention=True) is the same switch for one
 #                              model.  Forward only: under grad mode, on 16-bit storage or on the CPU nothing changes.
+LLAMA_F32_ATTENTION_TRAIN = False  # True: a float32 LlamaEncoder runs the attention of its packed pass UNDER GRAD MODE on
+#                                    `ops.causal_attn_f32_train` (the forward kernel above with lse, and its backward
+#                                    causal_attn_f32_bwd.hip: dQ and dK/dV on the f32-input MFMA, deterministic; one forward and
+#                                    one backward call per block) instead of one SDPA call per sequence differentiated by autograd.
+#                                    `LlamaEncoder.f32_attention_train` / ModelForTraining(f32_attention=True) is the same switch
+#                                    for one model.  Under no-grad, on 16-bit storage, on the CPU or off the packed path nothing
+#                                    changes; LLAMA_F32_ATTENTION stays "no-grad only".
 FWD128_ONE_WAVE = True   # head_dim 128 with 4 (8, ..) q heads per kv head: the forward walks its own list (64 queries x 4 heads per entry)
 #                          with the one-wave-per-SIMD kernel (ops.FWD_ONE_WAVE_HEAD_DIMS names the head dims); False: the 128-query kernel
 #                          of rounds 3-4 (the A/B arm of `bench.py --fwd128 classic`)
@@ -215,11 +222,23 @@ class VarlenCtx:
     work lists: `tiles` (128 queries per entry: forward and dQ), `k_tiles` (dK/dV), `fwd_tiles` (the forward's own list where it has
     one -- head_dim 128: 64 queries x 4 q heads per entry, `ops.attn_fwd_tile_table` -- else None); the work lists of
     `ops.causal_attn_f32` where the f32 attention was opted in (else None): `f32_tiles` for the full blocks (lens, lens) and
-    `f32_last_tiles` for the last block's one query per sequence ([1] * N, lens)."""
+    `f32_last_tiles` for the last block's one query per sequence ([1] * N, lens); under grad mode with the f32 TRAINING attention
+    opted in, the same two query lists and the key lists of `ops.causal_attn_f32_train` beside them (`f32_k_tiles`,
+    `f32_last_k_tiles`; else None), which is what sends the attention there."""
 
-    def __init__(self, cu, lens, max_len, tiles=None, k_tiles=None, fwd_tiles=None, f32_tiles=None, f32_last_tiles=None):
+    def __init__(self, cu, lens, max_len, tiles=None, k_tiles=None, fwd_tiles=None, f32_tiles=None, f32_last_tiles=None,
+                 f32_k_tiles=None, f32_last_k_tiles=None):
         self.cu, self.lens, self.max_len, self.tiles, self.k_tiles, self.fwd_tiles = cu, lens, max_len, tiles, k_tiles, fwd_tiles
         self.f32_tiles, self.f32_last_tiles = f32_tiles, f32_last_tiles
+        self.f32_k_tiles, self.f32_last_k_tiles = f32_k_tiles, f32_last_k_tiles
+
+
+def _ckpt_single_input(ctx) -> bool:
+    """Whether a checkpointed block receives x + delta as ONE tensor (CKPT_SINGLE_INPUT).  Not on the f32 training attention
+    path: there the block receives the (x, delta) pair an un-checkpointed block receives, so that the sum is formed, and its
+    gradient rounded, inside the same fused add + RMSNorm in both -- the checkpointed step of that path is then the plain step
+    bit for bit, at the price of a second [tokens, d] tensor kept per checkpointed block."""
+    return CKPT_SINGLE_INPUT and not (isinstance(ctx, VarlenCtx) and ctx.f32_k_tiles is not None)
 
 
 def _varlen_causal_attention(q, k, v, ctx: VarlenCtx):
@@ -237,6 +256,11 @@ def _varlen_causal_attention(q, k, v, ctx: VarlenCtx):
     if ctx.f32_tiles is not None and not torch.is_grad_enabled() and _ops.causal_attn_f32_ok(q, k, v):
         # f32 storage, opted in (LLAMA_F32_ATTENTION / f32_attention), no-grad: one launch of the f32-MFMA kernel for the batch
         return _ops.causal_attn_f32(q, k, v, ctx.cu, ctx.cu, ctx.f32_tiles, 1.0 / math.sqrt(q.shape[-1]))[0].view(q.shape)
+    if ctx.f32_k_tiles is not None and torch.is_grad_enabled() and _ops.causal_attn_f32_ok(q, k, v):
+        # f32 storage, opted in (LLAMA_F32_ATTENTION_TRAIN / f32_attention_train), grad mode: the same kernel with lse, and its
+        # backward as ONE autograd node
+        return _ops.causal_attn_f32_train(q, k, v, ctx.cu, ctx.cu, ctx.f32_tiles, ctx.f32_k_tiles,
+                                          1.0 / math.sqrt(q.shape[-1])).view(q.shape)
     outs, o0 = [], 0                      # f32 or CPU (tests, config 1): one SDPA call per sequence
     for n in ctx.lens:
         a = F.scaled_dot_product_attention(q[o0:o0 + n].transpose(0, 1)[None], k[o0:o0 + n].transpose(0, 1)[None],
@@ -258,6 +282,11 @@ def _varlen_last_query_attention(q, k, v, ctx: VarlenCtx):
         # the same kernel with one query per sequence: bottom-right aligned, so that query sees every key
         cu_q = torch.arange(N + 1, device=q.device, dtype=torch.int32)
         return _ops.causal_attn_f32(q, k, v, cu_q, ctx.cu, ctx.f32_last_tiles, 1.0 / math.sqrt(q.shape[-1]))[0].view(q.shape)
+    if ctx.f32_last_k_tiles is not None and torch.is_grad_enabled() and _ops.causal_attn_f32_ok(q, k, v):
+        # grad mode, opted in (LLAMA_F32_ATTENTION_TRAIN / f32_attention_train): the one-query form of the same autograd node
+        cu_q = torch.arange(N + 1, device=q.device, dtype=torch.int32)
+        return _ops.causal_attn_f32_train(q, k, v, cu_q, ctx.cu, ctx.f32_last_tiles, ctx.f32_last_k_tiles,
+                                          1.0 / math.sqrt(q.shape[-1])).view(q.shape)
     outs, o0 = [], 0
     for i, n in enumerate(ctx.lens):
         a = F.scaled_dot_product_attention(q[i:i + 1].transpose(0, 1)[None], k[o0:o0 + n].transpose(0, 1)[None],
@@ -493,6 +522,7 @@ class LlamaEncoder(nn.Module):
         self.hand_attention = True         # False: PyTorch's own flash-attention ops both ways (the "stock flash" control of
         #                                    bench.step_parity; a Python attribute, not an environment switch)
         self.f32_attention = False         # True: as LLAMA_F32_ATTENTION, for this model (float32 storage, no-grad packed pass)
+        self.f32_attention_train = False   # True: as LLAMA_F32_ATTENTION_TRAIN, for this model (float32 storage, grad mode)
         self.apply(self._init)
 
     def _init(self, m):
@@ -514,7 +544,7 @@ class LlamaEncoder(nn.Module):
         self.checkpoint_layers = None if layers == "all" else layers
         self.memory_plan = None
 
-    def _checkpointed_blocks(self, tokens: int) -> int:
+    def _checkpointed_blocks(self, tokens: int, single_input: bool = None) -> int:
         """How many of the first blocks run under torch.utils.checkpoint for a step of `tokens` padded tokens.  "auto" plans once
         per LARGEST token count seen (a longer batch re-plans: only ever towards more checkpointing, so the plan holds for every
         batch so far) and hands ops the verdict on the transposed d(gate|up) buffer."""
@@ -524,7 +554,8 @@ class LlamaEncoder(nn.Module):
             return int(self.checkpoint_layers)
         if self.memory_plan is None or tokens > self.memory_plan.tokens:
             from . import memory
-            plan = memory.plan_for_encoder(self, tokens, block_inputs=1 if CKPT_SINGLE_INPUT else 2, **self.memory_plan_hints)
+            plan = memory.plan_for_encoder(self, tokens, block_inputs=1 if (CKPT_SINGLE_INPUT if single_input is None else single_input) else 2,
+                                            **self.memory_plan_hints)
             if self.memory_plan is not None:
                 plan.checkpoint_blocks = max(plan.checkpoint_blocks, self.memory_plan.checkpoint_blocks)
             self.memory_plan = plan
@@ -600,11 +631,12 @@ class LlamaEncoder(nn.Module):
 
     def _run_layers(self, x, rope, ctx, upto=None, tokens=None):
         ck = self.gradient_checkpointing and self.training and torch.is_grad_enabled()
-        nck = self._checkpointed_blocks(x.shape[0] * x.shape[1] if tokens is None else tokens) if ck else 0
+        single = _ckpt_single_input(ctx)
+        nck = self._checkpointed_blocks(x.shape[0] * x.shape[1] if tokens is None else tokens, single) if ck else 0
         delta = None
         for i, layer in enumerate(self.layers if upto is None else self.layers[:upto]):
             if ck and i < nck:
-                if CKPT_SINGLE_INPUT and delta is not None:
+                if single and delta is not None:
                     x, delta = x + delta, None
                 x, delta = checkpoint(layer, x, delta, rope, ctx, use_reentrant=False, context_fn=_checkpoint_contexts)
             else:
@@ -693,16 +725,27 @@ class LlamaEncoder(nn.Module):
             # opted in: the work lists of ops.causal_attn_f32 from the host lengths, uploaded asynchronously
             f32_tiles = _ops.causal_attn_f32_tile_table(lens, lens, x.device)
             f32_last_tiles = _ops.causal_attn_f32_tile_table([1] * N, lens, x.device)
-        ctx = VarlenCtx(cu, lens, max(lens), tiles, k_tiles, fwd_tiles, f32_tiles, f32_last_tiles)
+        f32_k_tiles = f32_last_k_tiles = None
+        if ((LLAMA_F32_ATTENTION_TRAIN or self.f32_attention_train) and x.is_cuda and x.dtype == torch.float32
+                and torch.is_grad_enabled()
+                and _ops.causal_attn_f32_shape_ok(self.config.num_attention_heads, self.config.num_key_value_heads,
+                                                  self.config.head_dim)):
+            # opted in, grad mode: the same two query lists and the key lists of ops.causal_attn_f32_train
+            f32_tiles = _ops.causal_attn_f32_tile_table(lens, lens, x.device)
+            f32_last_tiles = _ops.causal_attn_f32_tile_table([1] * N, lens, x.device)
+            f32_k_tiles = _ops.causal_attn_f32_key_tile_table(lens, lens, x.device)
+            f32_last_k_tiles = _ops.causal_attn_f32_key_tile_table([1] * N, lens, x.device)
+        ctx = VarlenCtx(cu, lens, max(lens), tiles, k_tiles, fwd_tiles, f32_tiles, f32_last_tiles, f32_k_tiles=f32_k_tiles,
+                        f32_last_k_tiles=f32_last_k_tiles)
         last_idx = (cu[1:] - 1).to(torch.int64)
         # the plan's token count is the PADDED one (every row at its batch's full width): what the collator can hand over at worst
         tok_pad = sum(m.shape[0] * m.shape[1] for _, m in batches)
         x, delta = self._run_layers(x, rope, ctx, upto=len(self.layers) - 1, tokens=tok_pad)
         li = len(self.layers) - 1
         ck = self.gradient_checkpointing and self.training and torch.is_grad_enabled()
-        nck = self._checkpointed_blocks(tok_pad) if ck else 0
+        nck = self._checkpointed_blocks(tok_pad, _ckpt_single_input(ctx)) if ck else 0
         if ck and li < nck:
-            if CKPT_SINGLE_INPUT and delta is not None:
+            if _ckpt_single_input(ctx) and delta is not None:
                 x, delta = x + delta, None
             last = checkpoint(self.layers[li].forward_last_rows, x, delta, rope, ctx, last_idx, use_reentrant=False,
                               context_fn=_checkpoint_contexts)

@@ -83,12 +83,20 @@ class ModelForTraining(nn.Module):
         config=None,
         torch_dtype=None,
         unpad: bool = True,
+        f32_attention: bool = False,
     ):
+        """f32_attention: a float32 Llama encoder runs the attention of its packed pass on the hand-written f32-MFMA kernels, under
+        grad mode (`LlamaEncoder.f32_attention_train`, `ops.causal_attn_f32_train`: forward and backward, one call each per
+        block) and under no-grad (`LlamaEncoder.f32_attention`: eval-mode scoring), instead of one SDPA call per sequence; off by
+        default, and without effect on 16-bit models and BERT-family encoders."""
         super().__init__()
         self.unpad = unpad
         # attn_implementation / use_cache / cache_dir / token / trust_remote_code are accepted for signature
         # compatibility; attention always runs through torch SDPA (flash on ROCm) and there is no KV cache.
         self.model = _load_or_build(model_name_or_path, encoder, config, torch_dtype)
+        if f32_attention and hasattr(self.model, "f32_attention_train"):
+            self.model.f32_attention = True
+            self.model.f32_attention_train = True
         self.criterion = nn.CrossEntropyLoss(reduction="mean")     # kept for attribute parity (modeling.py:179)
 
         self.normalize_embeddings = normalize_embeddings

@@ -1302,6 +1302,100 @@ def causal_attn_f32(q, k, v, cu_q, cu_k, tiles, scale, want_lse: bool = False):
     return out, lse
 
 
+# ------------------------------------------------------------------------------------------------
+# (9d) the backward of (9c) and the autograd Function over the pair: the attention of the packed f32 Llama TRAINING pass
+# (opt-in: encoder.LLAMA_F32_ATTENTION_TRAIN).  Header section (9d), rankpo_amd/csrc/causal_attn_f32_bwd.hip.
+# ------------------------------------------------------------------------------------------------
+def causal_attn_f32_key_tile_list(lens_q, lens_k):
+    """The key work list of `causal_attn_f32_bwd` as a host numpy int32 [n, 2] = (sequence id, first key row): one entry per
+    (sequence with keys, block of 32 keys), sequences without queries included (their dk / dv rows are zero-filled).  An entry
+    walks the queries that see its first key, lq - max(0, k0 - (lk - lq)) of them: the entries with the most come first.
+    Raises ValueError in the cases `causal_attn_f32_tile_list` does."""
+    import numpy as np
+    kb = CAUSAL_ATTN_F32_Q_BLOCK
+    lq = np.asarray(lens_q, dtype=np.int64).reshape(-1)
+    lk = np.asarray(lens_k, dtype=np.int64).reshape(-1)
+    if lq.shape != lk.shape:
+        raise ValueError("causal_attn_f32_key_tile_list: one query length and one key length per sequence")
+    if (lq > lk).any() or (lq < 0).any():
+        raise ValueError("causal_attn_f32_key_tile_list: 0 <= lens_q[n] <= lens_k[n] is required (bottom-right aligned causal mask)")
+    nt = (lk + kb - 1) // kb
+    seq = np.repeat(np.arange(len(lk)), nt)
+    k0 = (np.arange(int(nt.sum())) - np.repeat(np.cumsum(nt) - nt, nt)) * kb
+    visible = lq[seq] - np.maximum(0, k0 - (lk - lq)[seq])
+    order = np.argsort(-visible, kind="stable")
+    return np.stack([seq[order], k0[order]], 1).astype(np.int32).reshape(-1, 2)
+
+
+def causal_attn_f32_key_tile_table(lens_q, lens_k, device):
+    """`causal_attn_f32_key_tile_list` on the device: a pinned, asynchronous upload (nothing waits for it on the host)."""
+    t = torch.from_numpy(causal_attn_f32_key_tile_list(lens_q, lens_k))
+    if torch.device(device).type == "cuda":
+        t = t.pin_memory()
+    return t.to(device, non_blocking=True)
+
+
+def causal_attn_f32_bwd(q, k, v, out, lse, dout, cu_q, cu_k, tiles, k_tiles, scale):
+    """The gradients of `causal_attn_f32`: (dq [Tq, nh, hd], dk [Tk, nkv, hd], dv [Tk, nkv, hd]), float32, from its inputs, its
+    results (out [Tq, nh * hd], lse [nh, Tq]) and dout (the shape of out or of q).  tiles as the forward's, k_tiles from
+    `causal_attn_f32_key_tile_table` on the same lengths.  One entry, two launches (dQ, then dK/dV), no atomics: deterministic,
+    and independent of what else is packed in the batch.  The raw op: no autograd node."""
+    if not causal_attn_f32_ok(q, k, v):
+        raise ValueError("causal_attn_f32_bwd: float32 HIP tensors [T, heads, head_dim] with head_dim in (64, 128), 1 / 2 / 4 / 8 "
+                         "query heads per kv head, heads contiguous, 16-byte aligned, token strides % 4 == 0")
+    if (cu_q.numel() != cu_k.numel() or cu_q.dtype != torch.int32 or cu_k.dtype != torch.int32 or tiles.dtype != torch.int32
+            or k_tiles.dtype != torch.int32 or tiles.dim() != 2 or k_tiles.dim() != 2 or tiles.shape[1] != k_tiles.shape[1]):
+        raise ValueError("causal_attn_f32_bwd: cu_q / cu_k int32 [N + 1], tiles / k_tiles int32 [n, 2]")
+    Tq, nh, hd = q.shape
+    Tk, nkv, _ = k.shape
+    if (out.dtype != torch.float32 or dout.dtype != torch.float32 or lse.dtype != torch.float32 or out.numel() != q.numel()
+            or dout.numel() != q.numel() or lse.shape != (nh, Tq) or not lse.is_contiguous()):
+        raise ValueError("causal_attn_f32_bwd: out / dout float32 [Tq, nh * hd], lse float32 [nh, Tq] contiguous")
+
+    def rows(t):       # [Tq, nh * hd] with contiguous rows, 16-byte aligned, token stride % 4 == 0: as it is, else a copy
+        t = t.reshape(Tq, nh * hd)                      # a view wherever the strides allow one
+        if t.stride(1) != 1 or t.stride(0) % 4 or t.stride(0) <= 0 or t.data_ptr() % 16:
+            t = t.contiguous()
+        return t
+    out, dout = rows(out), rows(dout)
+    lib = _lib.load()
+    dq = torch.empty((Tq, nh, hd), dtype=torch.float32, device=q.device)
+    dk = torch.empty((Tk, nkv, hd), dtype=torch.float32, device=q.device)
+    dv = torch.empty((Tk, nkv, hd), dtype=torch.float32, device=q.device)
+    ws = torch.empty((nh, Tq, 2), dtype=torch.float32, device=q.device)
+    with torch.cuda.device(q.device):
+        check(lib.rpo_causal_attn_bwd_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(), q.stride(0),
+                                          k.stride(0), v.stride(0), out.stride(0), dout.stride(0), lse.data_ptr(), cu_q.data_ptr(),
+                                          cu_k.data_ptr(), tiles.data_ptr(), tiles.shape[0], k_tiles.data_ptr(), k_tiles.shape[0],
+                                          tiles.shape[1], CAUSAL_ATTN_F32_Q_BLOCK, cu_q.numel() - 1, nh, nkv, hd, float(scale),
+                                          dq.data_ptr(), nh * hd, dk.data_ptr(), nkv * hd, dv.data_ptr(), nkv * hd, ws.data_ptr(),
+                                          _stream(q)), "rpo_causal_attn_bwd_f32")
+    return dq, dk, dv
+
+
+class _CausalAttnF32Train(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, cu_q, cu_k, tiles, k_tiles, scale):
+        out, lse = causal_attn_f32(q, k, v, cu_q, cu_k, tiles, scale, want_lse=True)
+        ctx.save_for_backward(q, k, v, out, lse, cu_q, cu_k, tiles, k_tiles)
+        ctx.scale = scale
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse, cu_q, cu_k, tiles, k_tiles = ctx.saved_tensors
+        dq, dk, dv = causal_attn_f32_bwd(q, k, v, out, lse, dout, cu_q, cu_k, tiles, k_tiles, ctx.scale)
+        return dq, dk, dv, None, None, None, None, None
+
+
+def causal_attn_f32_train(q, k, v, cu_q, cu_k, tiles, k_tiles, scale):
+    """`causal_attn_f32` with a gradient: an autograd Function over (q, k, v), column-block views of the fused projection output
+    included.  Forward: `causal_attn_f32(..., want_lse=True)` (the same deterministic kernel, also when a checkpointed block
+    recomputes it); saved: q, k, v, out, lse; backward: ONE call of `causal_attn_f32_bwd` (dout of any stride: made contiguous
+    only if needed).  Returns out [Tq, nh * hd]."""
+    return _CausalAttnF32Train.apply(q, k, v, cu_q, cu_k, tiles, k_tiles, scale)
+
+
 def add_layernorm(a, b, weight, bias, eps, out=None):
     """LayerNorm(a + b) * weight + bias over the last dim of 2-D row-strided a / b (b may be None); a + b rounded to the storage
     dtype first.  out: [rows, d] (row stride free) or None (a new contiguous tensor)."""
