@@ -105,12 +105,19 @@ def llama_forward(w: dict, cfg: dict, input_ids: torch.Tensor, attention_mask: t
 
 
 def _ln(x, w, b, eps):
+    # HF BertModel's nn.LayerNorm on 16-bit storage: statistics and the affine map in float32, ONE rounding of the result (as
+    # `_rms` / `_softmax` above restate HF's float32 steps).  Rounding every elementwise step to the storage type instead made
+    # this control's error 1.5 x that of any LayerNorm kernel (tests/bert_encode_parity_util.py: the control spread).
+    if x.dtype in _LOW:
+        return _ln(x.float(), w.float(), b.float(), eps).to(x.dtype)
     mu = x.mean(-1, keepdim=True)
     var = ((x - mu) ** 2).mean(-1, keepdim=True)
     return (x - mu) / torch.sqrt(var + eps) * w + b
 
 
-def bert_forward(w: dict, cfg: dict, input_ids: torch.Tensor, attention_mask: torch.Tensor, dtype=torch.float32):
+def bert_forward(w: dict, cfg: dict, input_ids: torch.Tensor, attention_mask: torch.Tensor, dtype=torch.float32,
+                 token_type_ids=None):
+    """token_type_ids [N, L] (None: every token is of type 0, HF's default) select the rows of the token-type table."""
     W = lambda k: w[k].to(dtype)
     d, nh, eps = cfg["hidden_size"], cfg["num_attention_heads"], cfg["layer_norm_eps"]
     hd = d // nh
@@ -122,7 +129,8 @@ def bert_forward(w: dict, cfg: dict, input_ids: torch.Tensor, attention_mask: to
         pos = W("embeddings.position_embeddings.weight")[torch.cumsum(keep, 1) * keep + pad]
     else:
         pos = W("embeddings.position_embeddings.weight")[:L][None]
-    x = W("embeddings.word_embeddings.weight")[input_ids] + W("embeddings.token_type_embeddings.weight")[0] + pos
+    tt = W("embeddings.token_type_embeddings.weight")
+    x = W("embeddings.word_embeddings.weight")[input_ids] + (tt[0] if token_type_ids is None else tt[token_type_ids]) + pos
     x = _ln(x, W("embeddings.LayerNorm.weight"), W("embeddings.LayerNorm.bias"), eps)
     bias = torch.zeros(N, 1, 1, L, dtype=dtype, device=x.device).masked_fill(~attention_mask.bool()[:, None, None, :],
                                                                              torch.finfo(dtype).min)
@@ -140,16 +148,17 @@ def bert_forward(w: dict, cfg: dict, input_ids: torch.Tensor, attention_mask: to
     return x
 
 
-def encoder_forward(w, cfg, input_ids, attention_mask, dtype=torch.float32, block_checkpoint=False):
+def encoder_forward(w, cfg, input_ids, attention_mask, dtype=torch.float32, block_checkpoint=False, token_type_ids=None):
     arch = (cfg.get("architectures") or ["Llama"])[0]
     if "Llama" in arch:
         return llama_forward(w, cfg, input_ids, attention_mask, dtype, block_checkpoint=block_checkpoint)
-    return bert_forward(w, cfg, input_ids, attention_mask, dtype)
+    return bert_forward(w, cfg, input_ids, attention_mask, dtype, token_type_ids=token_type_ids)
 
 
 def embed(w, cfg, inputs, normalize=True, dtype=torch.float32, force_last=False, block_checkpoint=False):
     """ModelForTraining.embed (modeling.py:206-238) / RankPOTrainer.single_forward (rankpo_trainer.py:392-418)."""
-    h = encoder_forward(w, cfg, inputs["input_ids"], inputs["attention_mask"], dtype, block_checkpoint=block_checkpoint)
+    h = encoder_forward(w, cfg, inputs["input_ids"], inputs["attention_mask"], dtype, block_checkpoint=block_checkpoint,
+                        token_type_ids=inputs.get("token_type_ids"))
     m = inputs["attention_mask"]
     arch = (cfg.get("architectures") or ["Llama"])[0]
     if force_last or "Llama" in arch:

@@ -168,13 +168,14 @@ TABLE_HEAD = ("| arm | worst row (length) | err fast | err eager | err flash | b
               "rms flash |")
 
 
-def rule(ref, fast, eager, flash, lens, arm="", row_factor=None, out=print):
+def rule(ref, fast, eager, flash, lens, arm="", row_factor=None, out=print, floor=FLOOR, guard_floor=GUARD_FLOOR):
     """The rule of the module docstring.  ref: float64 unit rows [N, d]; fast / eager / flash: [N, d] tensors (or arrays) of any
     float type; `flash` may be None (storage without hand-written attention has no such control); lens: the N token counts.
-    `row_factor`: the per-row factor (None: ROW_FACTOR); above ROW_FACTOR_CAP it is refused.  Returns the failures as dicts (kind:
-    "row" over its bound, "missing" / "shape" / "nonfinite" = the fast path has no such row, "control" = a control has none,
-    "guard" = the two controls disagree, "rms" = the case's RMS (row None), "extra" = more rows than sequences (row N); row, len;
-    fast, eager, flash, bound) and prints one table row: the row that uses most of its bound."""
+    `row_factor`: the per-row factor (None: ROW_FACTOR); above ROW_FACTOR_CAP it is refused.  `floor` / `guard_floor`: the additive
+    terms of the bounds and of the guard (tests/bert_encode_parity_util.py scales them by the storage type's round-off).
+    Returns the failures as dicts (kind: "row" over its bound, "missing" / "shape" / "nonfinite" = the fast path has no such row,
+    "control" = a control has none, "guard" = the two controls disagree, "rms" = the case's RMS (row None), "extra" = more rows
+    than sequences (row N); row, len; fast, eager, flash, bound) and prints one table row: the row that uses most of its bound."""
     row_factor = ROW_FACTOR if row_factor is None else row_factor
     if not row_factor <= ROW_FACTOR_CAP:
         raise ValueError(f"per-row factor {row_factor} > {ROW_FACTOR_CAP}: if the controls alone need more, change the case")
@@ -190,7 +191,7 @@ def rule(ref, fast, eager, flash, lens, arm="", row_factor=None, out=print):
             fails.append(dict(rec, kind="control"))
             continue
         ctrl = max(e, l) if l is not None else e
-        rec["bound"] = row_factor * ctrl + FLOOR
+        rec["bound"] = row_factor * ctrl + floor
         if not isinstance(f, float):
             fails.append(dict(rec, kind=f))
         else:
@@ -198,14 +199,14 @@ def rule(ref, fast, eager, flash, lens, arm="", row_factor=None, out=print):
                 fails.append(dict(rec, kind="row"))
             if worst is None or f / rec["bound"] > worst["fast"] / worst["bound"]:
                 worst = dict(rec, ratio=f / max(ctrl, 1e-300))
-        if l is not None and not l <= GUARD * e + GUARD_FLOOR:
-            fails.append(dict(rec, kind="guard", bound=GUARD * e + GUARD_FLOOR))
+        if l is not None and not l <= GUARD * e + guard_floor:
+            fails.append(dict(rec, kind="guard", bound=GUARD * e + guard_floor))
     got_rows = None if fast is None or torch.as_tensor(fast).dim() != 2 else int(torch.as_tensor(fast).shape[0])
     if got_rows is not None and got_rows > N:
         fails.append(dict(kind="extra", row=N, len=None, fast=float(got_rows), eager=None, flash=None, bound=float(N)))
     rf, re_, rl = rms(ef), rms(ee), (rms(el) if el is not None else None)
     if rf is not None and re_ is not None and (el is None or rl is not None):
-        bound = FACTOR * max(re_, rl if rl is not None else 0.0) + FLOOR
+        bound = FACTOR * max(re_, rl if rl is not None else 0.0) + floor
         if not rf <= bound:
             fails.append(dict(kind="rms", row=None, len=None, fast=rf, eager=re_, flash=rl, bound=bound))
     fmt = lambda x: "-" if x is None else (x if isinstance(x, str) else f"{x:.3e}")
