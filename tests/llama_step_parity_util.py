@@ -184,13 +184,15 @@ def rel_err(got, ref):
     return float((g - ref).norm() / ref.norm().clamp_min(1e-300))
 
 
-def errors(step, ref, names, temperature=T_CONTRASTIVE):
+def errors(step, ref, names, temperature=T_CONTRASTIVE, score_scale=None):
     """A step (loss, scores, grads) against the reference (loss, scores, grads): `step_parity`'s loss and cosine statistics and
-    the per-tensor gradient errors.  loss / scores None: gradients only (an accumulated step has no single loss)."""
+    the per-tensor gradient errors.  loss / scores None: gradients only (an accumulated step has no single loss).  `score_scale`:
+    what turns a score difference into a cosine difference; None = `temperature` (InfoNCE's scores are cosines / T), 1.0 for a
+    head whose scores are the cosines themselves."""
     loss, scores, grads = step
     out = {"grad": {n: rel_err(grads.get(n), ref[2][n]) for n in names}}
     if loss is not None:
-        dc = (scores.detach().to("cpu", torch.float64) - ref[1]) * temperature
+        dc = (scores.detach().to("cpu", torch.float64) - ref[1]) * (temperature if score_scale is None else score_scale)
         out.update(loss_abs_err=abs(float(loss) - ref[0]), cos_rms_err=float(dc.pow(2).mean().sqrt()),
                    cos_max_err=float(dc.abs().max()))
     return out
@@ -199,16 +201,23 @@ def errors(step, ref, names, temperature=T_CONTRASTIVE):
 TABLE_HEAD = "| arm | worst tensor | err fast | err eager | err flash | bound | fast / larger control |"
 
 
-def rule(ref, fast, eager, flash, names, arm="", temperature=T_CONTRASTIVE, factors=None, out=print):
+def rule(ref, fast, eager, flash, names, arm="", temperature=T_CONTRASTIVE, factors=None, out=print, score_scale=None,
+         loss_lipschitz=None, metrics=None, metric_lipschitz=None, exact_metrics=()):
     """The rule of the module docstring.  ref / fast / eager / flash: (loss, scores, {name: grad}); `flash` may be None (an encoder
     without hand-written attention has no such control).  `factors`: {tensor name: factor} replacing 1.5 for that tensor on this
     arm -- a documented rounding point, see the caller's comment; nothing else is widened.  Returns the failures as dicts
     (kind: "grad" over its bound, "missing" = absent / None / wrong shape / non-finite, "control" = a control lacks the tensor,
     "guard" = the two controls disagree, "stat" = loss / cosine statistic; name; fast, eager, flash, bound) and prints one table
-    row: the tensor that uses most of its bound."""
+    row: the tensor that uses most of its bound.
+
+    For a head other than InfoNCE (tests/rankpo_step_parity_util.py): `score_scale` as in `errors`; `loss_lipschitz` = L, the
+    loss's Lipschitz constant in the cosines, which stands where InfoNCE has 1 / T (|d loss| <= L * cosine RMS error, floor
+    5e-6 * L).  `metrics` = (ref, fast, eager, flash-or-None) dicts of floats with `metric_lipschitz` = {key: L_k}: the fast
+    path's keys must be the reference's, every key of `metric_lipschitz` is held to 1.5 * max(control error, L_k * control cosine
+    RMS error) + 5e-6 * L_k, every key of `exact_metrics` must equal the reference's value (kind "metric")."""
     factors = factors or {}
-    ef, ee = errors(fast, ref, names, temperature), errors(eager, ref, names, temperature)
-    el = errors(flash, ref, names, temperature) if flash is not None else None
+    ef, ee = errors(fast, ref, names, temperature, score_scale), errors(eager, ref, names, temperature, score_scale)
+    el = errors(flash, ref, names, temperature, score_scale) if flash is not None else None
     fails, worst = [], None
     for n in names:
         f, e, l = ef["grad"][n], ee["grad"][n], (el["grad"][n] if el is not None else None)
@@ -232,12 +241,34 @@ def rule(ref, fast, eager, flash, names, arm="", temperature=T_CONTRASTIVE, fact
         ctrl = {k: max(c[k] for c in both) for k in ("loss_abs_err", "cos_rms_err", "cos_max_err")}
         tol = {"cos_rms_err": FACTOR * ctrl["cos_rms_err"] + COS_FLOOR, "cos_max_err": FACTOR * ctrl["cos_max_err"] + COS_FLOOR,
                "loss_abs_err": FACTOR * max(ctrl["loss_abs_err"], ctrl["cos_rms_err"] / temperature) + COS_FLOOR / temperature}
+        if loss_lipschitz is not None:
+            tol["loss_abs_err"] = FACTOR * max(ctrl["loss_abs_err"], loss_lipschitz * ctrl["cos_rms_err"]) + COS_FLOOR * loss_lipschitz
         for k, t in tol.items():
             rec = dict(name=k, fast=ef[k], eager=ee[k], flash=el[k] if el is not None else None, bound=t)
             if not ef[k] <= t:
                 fails.append(dict(rec, kind="stat"))
             if el is not None and k != "loss_abs_err" and not el[k] <= GUARD * ee[k] + GUARD_FLOOR:
                 fails.append(dict(rec, kind="guard", bound=GUARD * ee[k] + GUARD_FLOOR))
+    if metrics is not None:
+        assert "loss_abs_err" in ef, "metrics are judged against the controls' cosine error: the steps need their scores"
+        mr, mf, me, ml = metrics
+        assert (ml is None) == (flash is None)
+        ctrls = [me] + ([ml] if ml is not None else [])
+        for k in sorted(set(mr) | set(mf)):
+            if k not in mr or k not in mf or any(k not in c for c in ctrls):
+                fails.append(dict(name=k, kind="metric", fast=None, eager=None, flash=None, bound=None))
+                continue
+            err = lambda m: abs(float(m[k]) - float(mr[k]))
+            rec = dict(name=k, fast=err(mf), eager=err(me), flash=err(ml) if ml is not None else None, bound=None)
+            if k in exact_metrics:
+                rec["bound"] = 0.0
+            elif k in (metric_lipschitz or {}):
+                lk = metric_lipschitz[k]
+                rec["bound"] = FACTOR * max(max(err(c) for c in ctrls), lk * ctrl["cos_rms_err"]) + COS_FLOOR * lk
+            else:
+                raise KeyError(f"metric {k} has neither a Lipschitz constant nor an exact comparison")
+            if not rec["fast"] <= rec["bound"]:
+                fails.append(dict(rec, kind="metric"))
     fmt = lambda x: "-" if x is None else f"{x:.3e}"
     if worst is not None:
         out(f"| {arm} | {worst['name']} | {fmt(worst['fast'])} | {fmt(worst['eager'])} | {fmt(worst['flash'])} | "
