@@ -20,7 +20,7 @@
  * write gradients for exactly those rows, which is what removes the backward collective.
  *
  * Embedding matrices are row-major [rows, d] with a contiguous inner dimension; dtype selects the
- * storage type of embeddings / hidden states / scores (f32 or bf16; accumulation is always f32).
+ * storage type of embeddings / hidden states / scores (f32, bf16 or fp16; accumulation is always f32).
  */
 #ifndef RANKPO_HIP_H
 #define RANKPO_HIP_H
@@ -503,6 +503,38 @@ int rpo_causal_attn_bwd_f32(const void* q, const void* k, const void* v, const v
                             int64_t nktiles, int64_t tile_cols, int64_t q_block, int64_t num_seqs, int64_t num_heads,
                             int64_t num_kv_heads, int64_t head_dim, float scale, void* dq, int64_t dq_stride, void* dk,
                             int64_t dk_stride, void* dv, int64_t dv_stride, float* ws, rpo_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * (9e) causal fp16 attention of the packed Llama pass (rankpo_amd/csrc/causal_attn_f16.hip; opt-in: encoder.LLAMA_FP16_NATIVE /
+ * LlamaEncoder.native_fp16, ModelForInference(native_fp16=True): the reference's ModelForInference(use_fp16=True),
+ * modeling.py:453-454, for a Llama encoder, whose attention HF runs as softmax(Q K^T / sqrt(d) + causal mask) V).  Forward only,
+ * for no-grad callers; no allocation, no host sync, no atomics: deterministic, and a sequence's rows do not depend on what else
+ * is packed.
+ *
+ * rpo_causal_attn_fwd_f16: the contract of (9c) on fp16 storage, in the argument order of rpo_causal_attn_fwd_f32.  q: [total_q,
+ * num_heads, head_dim], k / v: [T_k, num_kv_heads, head_dim], fp16, token strides in ELEMENTS, heads contiguous (column blocks of
+ * the fused q|k|v or k|v projection output, read as they lie); out: fp16 [total_q, num_heads * head_dim] with token stride
+ * out_stride.  Query head h reads kv head h / (num_heads / num_kv_heads).  cu_seqlens_q / cu_seqlens_k: int32 [num_seqs + 1] on
+ * the device; query i of a sequence with lq queries and lk keys sees key j iff j <= i + (lk - lq) (bottom-right aligned: lq == lk
+ * is causal self-attention, lq == 1 is one query over every key).  lq <= lk is the caller's precondition; rows of a sequence that
+ * breaks it come out as zeros with lse = -inf where they see no key.  Masked keys of a step get p = 0 and never enter the
+ * running maximum; key steps past an entry's last visible key are not executed; no access leaves the sequence.
+ * tiles: int32 [ntiles][2] = (sequence id, first query row inside the sequence), 32 query rows per entry, the format of (9c),
+ * built on the host from the lengths; one block per (entry, kv head), one wave per query head of the group, K / V steps staged
+ * once per kv head in LDS (V transposed, so that P enters the PV product as it lies in the accumulators).
+ * Arithmetic: S and PV on v_mfma_f32_16x16x32_f16 with f32 accumulation; raw scores stay f32 and are never stored as fp16; the
+ * scale is applied in f32 (Q is not pre-scaled): p = exp2(((s - m) |scale|) log2(e)) with m the running maximum of the raw
+ * scores; P is rounded to fp16 exactly once, as the PV operand, and the row sum adds the same rounded P; the output is divided in
+ * f32 and rounded to fp16 once (overflow gives inf).  lse (may be NULL: not written): f32 [num_heads][total_q], natural log,
+ * total_q = cu_seqlens_q[num_seqs] as the kernel reads it.
+ * head_dim 64 or 128; num_heads / num_kv_heads in {1, 2, 4, 8}; tile_cols == 2, q_block == 32; q / k / v / out 16-byte aligned
+ * with token strides % 8 == 0: anything else is RPO_ERR_UNSUPPORTED before any launch.  ntiles == 0 is RPO_OK and launches
+ * nothing.
+ * --------------------------------------------------------------------------------------------- */
+int rpo_causal_attn_fwd_f16(const void* q, const void* k, const void* v, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                            const int* cu_seqlens_q, const int* cu_seqlens_k, const int* tiles, int64_t ntiles,
+                            int64_t tile_cols, int64_t q_block, int64_t num_seqs, int64_t num_heads, int64_t num_kv_heads,
+                            int64_t head_dim, float scale, void* out, int64_t out_stride, float* lse, rpo_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * (10) packed TRAINING step of the BERT / XLM-R block (rankpo_amd/csrc/bert_ops.hip; BertEncoder.pooled_cls_train, used by

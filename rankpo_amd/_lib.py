@@ -102,6 +102,8 @@ SIGNATURES = {
                                             _vp]),
     "rpo_causal_attn_fwd_f32": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                           _f32, _vp, _i64, _vp, _vp]),
+    "rpo_causal_attn_fwd_f16": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                                          _f32, _vp, _i64, _vp, _vp]),
     "rpo_causal_attn_bwd_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64,
                                           _i64, _i64, _i64, _i64, _i64, _i64, _f32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "rpo_bidir_attn_train_fwd": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64,

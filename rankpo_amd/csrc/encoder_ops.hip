@@ -294,7 +294,7 @@ extern "C" int rpo_transpose(const void* in, void* out, int64_t rows, int64_t co
 extern "C" int rpo_swiglu_fwd(const void* g, const void* u, void* out, int64_t rows, int64_t cols, int64_t ld_gu,
                               int64_t ld_out, int dtype, rpo_stream_t stream) {
     if (!g || !u || !out || rows <= 0 || cols <= 0) return RPO_ERR_INVALID_ARG;
-    const int V = dtype == RPO_DT_BF16 ? 8 : 4;
+    const int V = (dtype == RPO_DT_BF16 || dtype == RPO_DT_F16) ? 8 : 4;   // fp16: the forward only (no-grad Llama pass)
     if (cols % V != 0 || ld_gu % V != 0 || ld_out % V != 0 || ld_gu < cols || ld_out < cols || !rpo_aligned16(g) ||
         !rpo_aligned16(u) || !rpo_aligned16(out))
         return RPO_ERR_UNSUPPORTED;
@@ -307,6 +307,9 @@ extern "C" int rpo_swiglu_fwd(const void* g, const void* u, void* out, int64_t r
     else if (dtype == RPO_DT_F32)
         RPO_LAUNCH(swiglu_fwd_kernel<float>, dim3(ew_grid(nvec)), dim3(kEwThreads), 0, st, (const float*)g,
                    (const float*)u, (float*)out, rows, (int)(cols / V), ld_gu, ld_out);
+    else if (dtype == RPO_DT_F16)
+        RPO_LAUNCH(swiglu_fwd_kernel<f16_t>, dim3(ew_grid(nvec)), dim3(kEwThreads), 0, st, (const f16_t*)g,
+                   (const f16_t*)u, (f16_t*)out, rows, (int)(cols / V), ld_gu, ld_out);
     else
         return RPO_ERR_INVALID_ARG;
     return rpo_launch_status();
@@ -373,7 +376,7 @@ extern "C" int rpo_rope(const void* x_in, void* x, int64_t row_stride, const flo
                                 rpo_stream_t stream) {
     if (!x_in || !x || !cos_tab || !sin_tab || rows <= 0 || heads <= 0 || head_dim <= 0 || period <= 0)
         return RPO_ERR_INVALID_ARG;
-    const int V = dtype == RPO_DT_BF16 ? 8 : 4;
+    const int V = (dtype == RPO_DT_BF16 || (dtype == RPO_DT_F16 && !backward)) ? 8 : 4;   // fp16: the forward rotation only
     if ((head_dim / 2) % V != 0 || head_dim % 2 != 0 || row_stride % V != 0 || !rpo_aligned16(x) || !rpo_aligned16(x_in))
         return RPO_ERR_UNSUPPORTED;
     const int64_t pairs = heads * ((head_dim / 2) / V);
@@ -387,6 +390,9 @@ extern "C" int rpo_rope(const void* x_in, void* x, int64_t row_stride, const flo
                    sin_tab, rows, (int)heads, (int)head_dim, period, sign);
     else if (dtype == RPO_DT_F32)
         RPO_LAUNCH(rope_kernel<float>, dim3((unsigned)grid), dim3(kEwThreads), 0, st, (const float*)x_in, (float*)x, row_stride, cos_tab,
+                   sin_tab, rows, (int)heads, (int)head_dim, period, sign);
+    else if (dtype == RPO_DT_F16 && !backward)
+        RPO_LAUNCH(rope_kernel<f16_t>, dim3((unsigned)grid), dim3(kEwThreads), 0, st, (const f16_t*)x_in, (f16_t*)x, row_stride, cos_tab,
                    sin_tab, rows, (int)heads, (int)head_dim, period, sign);
     else
         return RPO_ERR_INVALID_ARG;
@@ -631,7 +637,7 @@ extern "C" int rpo_add_rmsnorm_fwd(const void* x, const void* delta, const void*
                                    rpo_stream_t stream) {
     if (!x || !weight || !y_out || !rstd_out || rows <= 0 || d <= 0) return RPO_ERR_INVALID_ARG;
     if (delta && !x_out) return RPO_ERR_INVALID_ARG;
-    const int V = dtype == RPO_DT_BF16 ? 8 : 4;
+    const int V = (dtype == RPO_DT_BF16 || dtype == RPO_DT_F16) ? 8 : 4;   // fp16: the forward only (no-grad Llama pass)
     if (d % V != 0 || !rpo_aligned16(x) || !rpo_aligned16(y_out) || !rpo_aligned16(weight) ||
         (delta && (!rpo_aligned16(delta) || !rpo_aligned16(x_out))))
         return RPO_ERR_UNSUPPORTED;
@@ -642,6 +648,7 @@ extern "C" int rpo_add_rmsnorm_fwd(const void* x, const void* delta, const void*
     const int nw = norm_waves(rows, RPO_NORM_FWD_CAP);       // (the forward writes no per-wave partials: its count is its own)
     if (dtype == RPO_DT_BF16) return launch_norm_fwd<bf16_t>(x, delta, weight, eps, x_out, y_out, rstd_out, rows, d, nw, st);
     if (dtype == RPO_DT_F32) return launch_norm_fwd<float>(x, delta, weight, eps, x_out, y_out, rstd_out, rows, d, nw, st);
+    if (dtype == RPO_DT_F16) return launch_norm_fwd<f16_t>(x, delta, weight, eps, x_out, y_out, rstd_out, rows, d, nw, st);
     return RPO_ERR_INVALID_ARG;
 }
 

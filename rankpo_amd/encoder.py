@@ -161,6 +161,14 @@ def _add_norm(x, delta, norm: "RMSNorm"):
     return x, norm(x)
 
 
+def _norm_rows(x, norm: "RMSNorm"):
+    """norm(x) on the few pooled rows of the last block: F.rms_norm as ever, except inside the native fp16 pass
+    (`ops.fp16_native`), where the fp16 row kernel takes these rows too."""
+    if x.dtype == torch.float16 and _ops.fused_norm_ok(x):
+        return _ops.add_rmsnorm(x, None, norm.weight, norm.eps)[1]
+    return norm(x)
+
+
 def _rotate_half(x):
     x1, x2 = x[..., : x.shape[-1] // 2], x[..., x.shape[-1] // 2:]
     return torch.cat((-x2, x1), dim=-1)
@@ -205,6 +213,15 @@ LLAMA_F32_ATTENTION_TRAIN = False  # True: a float32 LlamaEncoder runs the atten
 #                                    `LlamaEncoder.f32_attention_train` / ModelForTraining(f32_attention=True) is the same switch
 #                                    for one model.  Under no-grad, on 16-bit storage, on the CPU or off the packed path nothing
 #                                    changes; LLAMA_F32_ATTENTION stays "no-grad only".
+LLAMA_FP16_NATIVE = False  # True: a float16 LlamaEncoder runs its packed no-grad pass (ModelForInference.encode(use_fp16=True), the
+#                            RankPO ref_model, eval-mode scoring) on this project's HIP: the attention of every block, and the last
+#                            block's one-query form, on `ops.causal_attn_f16` (causal_attn_f16.hip, one launch each, on the strided
+#                            column blocks of the fused q|k|v output) instead of `aten._flash_attention_forward`; RMSNorm, RoPE and
+#                            the fused gate|up GEMM + SwiGLU on the fp16 instantiations of the row kernels (`ops.fp16_native`)
+#                            instead of F.rms_norm, the six-op rotary chain and two GEMMs + silu * mul.  GEMMs stay F.linear.
+#                            `LlamaEncoder.native_fp16` / ModelForInference(native_fp16=True) is the same switch for one model.
+#                            Forward only: under grad mode, on f32 / bf16 storage, on the CPU, for head dims or group sizes the
+#                            kernel refuses, or off the packed path (left-padded batches) nothing changes.
 FWD128_ONE_WAVE = True   # head_dim 128 with 4 (8, ..) q heads per kv head: the forward walks its own list (64 queries x 4 heads per entry)
 #                          with the one-wave-per-SIMD kernel (ops.FWD_ONE_WAVE_HEAD_DIMS names the head dims); False: the 128-query kernel
 #                          of rounds 3-4 (the A/B arm of `bench.py --fwd128 classic`)
@@ -224,7 +241,10 @@ class VarlenCtx:
     `ops.causal_attn_f32` where the f32 attention was opted in (else None): `f32_tiles` for the full blocks (lens, lens) and
     `f32_last_tiles` for the last block's one query per sequence ([1] * N, lens); under grad mode with the f32 TRAINING attention
     opted in, the same two query lists and the key lists of `ops.causal_attn_f32_train` beside them (`f32_k_tiles`,
-    `f32_last_k_tiles`; else None), which is what sends the attention there."""
+    `f32_last_k_tiles`; else None), which is what sends the attention there; the work lists of `ops.causal_attn_f16` where the
+    native fp16 pass was opted in (else None): `f16_tiles` (lens, lens) and `f16_last_tiles` ([1] * N, lens) -- attributes that
+    `pooled_last_token_multi` sets on the object (tests/test_llama_f32_train_host.py pins the constructor's parameter list)."""
+    f16_tiles = f16_last_tiles = None
 
     def __init__(self, cu, lens, max_len, tiles=None, k_tiles=None, fwd_tiles=None, f32_tiles=None, f32_last_tiles=None,
                  f32_k_tiles=None, f32_last_k_tiles=None):
@@ -250,6 +270,10 @@ def _varlen_causal_attention(q, k, v, ctx: VarlenCtx):
                                       k_tiles=ctx.k_tiles,
                                       key_block=_ops.ATTN_KEY_BLOCK if q.shape[-1] == 64 else _ops.ATTN_KEY_BLOCK_HD128,
                                       fwd_tiles=ctx.fwd_tiles)
+    if (ctx.f16_tiles is not None and q.dtype == torch.float16 and not torch.is_grad_enabled()
+            and _ops.causal_attn_f16_ok(q, k, v)):
+        # fp16 storage, opted in (LLAMA_FP16_NATIVE / native_fp16), no-grad: one launch of the fp16-MFMA kernel for the batch
+        return _ops.causal_attn_f16(q, k, v, ctx.cu, ctx.cu, ctx.f16_tiles, 1.0 / math.sqrt(q.shape[-1]))[0].view(q.shape)
     if q.is_cuda and q.dtype in (torch.bfloat16, torch.float16):
         return torch.ops.aten._flash_attention_forward(q, k, v, ctx.cu, ctx.cu, ctx.max_len, ctx.max_len, 0.0, True,
                                                        False)[0]
@@ -275,6 +299,11 @@ def _varlen_last_query_attention(q, k, v, ctx: VarlenCtx):
     """q [N, nh, hd]: ONE query per sequence (its last token); k/v [T, nkv, hd] packed.  The last token attends to
     every key of its own sequence, so no causal mask is needed."""
     N = q.shape[0]
+    if (ctx.f16_last_tiles is not None and q.dtype == torch.float16 and not torch.is_grad_enabled()
+            and _ops.causal_attn_f16_ok(q, k, v)):
+        # the same fp16 kernel with one query per sequence: bottom-right aligned, so that query sees every key
+        cu_q = torch.arange(N + 1, device=q.device, dtype=torch.int32)
+        return _ops.causal_attn_f16(q, k, v, cu_q, ctx.cu, ctx.f16_last_tiles, 1.0 / math.sqrt(q.shape[-1]))[0].view(q.shape)
     if q.is_cuda and q.dtype in (torch.bfloat16, torch.float16):
         cu_q = torch.arange(N + 1, device=q.device, dtype=torch.int32)
         return torch.ops.aten._flash_attention_forward(q, k, v, cu_q, ctx.cu, 1, ctx.max_len, 0.0, False, False)[0]
@@ -466,7 +495,7 @@ class LlamaLayer(nn.Module):
                 o = _ops.last_query_attn(q, kv, ctx.cu, att.nkv, att.hd, 1.0 / math.sqrt(att.hd))
                 xl = x[0].index_select(0, last_idx) + att.o_proj(o.reshape(-1, att.nh * att.hd))
                 # last_in_block: only the residual add follows, and an add saves nothing for backward
-                return xl + self.mlp(self.post_attention_layernorm(xl), last_in_block=True)
+                return xl + self.mlp(_norm_rows(xl, self.post_attention_layernorm), last_in_block=True)
             k, v = kv.split([nk, nk], dim=-1)
             k = k.view(T, att.nkv, att.hd)
         else:
@@ -478,7 +507,7 @@ class LlamaLayer(nn.Module):
             k = k * ck + _rotate_half(k) * sk
         o = _varlen_last_query_attention(q, k, v.view(T, att.nkv, att.hd), ctx)
         xl = x[0].index_select(0, last_idx) + att.o_proj(o.reshape(-1, att.nh * att.hd))
-        return xl + self.mlp(self.post_attention_layernorm(xl), last_in_block=True)
+        return xl + self.mlp(_norm_rows(xl, self.post_attention_layernorm), last_in_block=True)
 
 
 def _resized_embedding(old: nn.Embedding, n: int, std: float) -> nn.Embedding:
@@ -523,6 +552,7 @@ class LlamaEncoder(nn.Module):
         #                                    bench.step_parity; a Python attribute, not an environment switch)
         self.f32_attention = False         # True: as LLAMA_F32_ATTENTION, for this model (float32 storage, no-grad packed pass)
         self.f32_attention_train = False   # True: as LLAMA_F32_ATTENTION_TRAIN, for this model (float32 storage, grad mode)
+        self.native_fp16 = False           # True: as LLAMA_FP16_NATIVE, for this model (float16 storage, no-grad packed pass)
         self.apply(self._init)
 
     def _init(self, m):
@@ -735,8 +765,24 @@ class LlamaEncoder(nn.Module):
             f32_last_tiles = _ops.causal_attn_f32_tile_table([1] * N, lens, x.device)
             f32_k_tiles = _ops.causal_attn_f32_key_tile_table(lens, lens, x.device)
             f32_last_k_tiles = _ops.causal_attn_f32_key_tile_table([1] * N, lens, x.device)
+        f16_tiles = f16_last_tiles = None
+        if ((LLAMA_FP16_NATIVE or self.native_fp16) and x.is_cuda and x.dtype == torch.float16 and not torch.is_grad_enabled()
+                and _ops.causal_attn_f16_shape_ok(self.config.num_attention_heads, self.config.num_key_value_heads,
+                                                  self.config.head_dim)):
+            # opted in: the work lists of ops.causal_attn_f16 from the host lengths, uploaded asynchronously; the rest of the pass
+            # runs inside ops.fp16_native, which opens the fp16 row kernels
+            f16_tiles = _ops.causal_attn_f16_tile_table(lens, lens, x.device)
+            f16_last_tiles = _ops.causal_attn_f16_tile_table([1] * N, lens, x.device)
         ctx = VarlenCtx(cu, lens, max(lens), tiles, k_tiles, fwd_tiles, f32_tiles, f32_last_tiles, f32_k_tiles=f32_k_tiles,
                         f32_last_k_tiles=f32_last_k_tiles)
+        if f16_tiles is not None:
+            ctx.f16_tiles, ctx.f16_last_tiles = f16_tiles, f16_last_tiles
+            with _ops.fp16_native():
+                return self._pooled_rows(batches, x, rope, ctx, cu, n_fill)
+        return self._pooled_rows(batches, x, rope, ctx, cu, n_fill)
+
+    def _pooled_rows(self, batches, x, rope, ctx, cu, n_fill):
+        """The layers of `pooled_last_token_multi` on the packed tokens x [1, T, d], the final norm on the pooled rows."""
         last_idx = (cu[1:] - 1).to(torch.int64)
         # the plan's token count is the PADDED one (every row at its batch's full width): what the collator can hand over at worst
         tok_pad = sum(m.shape[0] * m.shape[1] for _, m in batches)
@@ -751,7 +797,7 @@ class LlamaEncoder(nn.Module):
                               context_fn=_checkpoint_contexts)
         else:
             last = self.layers[li].forward_last_rows(x, delta, rope, ctx, last_idx)         # [N, d]
-        pooled = self.norm(last)
+        pooled = _norm_rows(last, self.norm)
         if n_fill:
             pooled = pooled[:-1]
         return list(pooled.split([m.shape[0] for _, m in batches], 0))

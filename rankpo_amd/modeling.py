@@ -256,13 +256,18 @@ class ModelForInference(nn.Module):
         tokenizer=None,
         packed_f32: bool = False,
         f32_attention: bool = False,
+        native_fp16: bool = False,
     ) -> None:
         """packed_f32: a float32 BERT-family encoder (neither use_fp16 nor use_bf16) runs `encode()` on the packed f32 forward
         (`BertEncoder.native_f32`) instead of the padded PyTorch path; off by default, BERT family only: ignored for Llama (see
         f32_attention) and 16-bit models.
         f32_attention: a float32 Llama encoder runs the attention of its packed `encode()` pass on the hand-written f32-MFMA
         kernel (`LlamaEncoder.f32_attention`, `ops.causal_attn_f32`: one launch per block) instead of one SDPA call per sequence;
-        off by default, ignored for the BERT family and 16-bit models."""
+        off by default, ignored for the BERT family and 16-bit models.
+        native_fp16: a float16 Llama encoder (use_fp16, the reference's modeling.py:453-454) runs its packed `encode()` pass on the
+        hand-written fp16 kernels (`LlamaEncoder.native_fp16`: `ops.causal_attn_f16`, one launch per block, and the fp16 RMSNorm /
+        RoPE / SwiGLU row kernels) instead of `aten._flash_attention_forward` and eager PyTorch; off by default, ignored for the
+        BERT family and for models that are not float16 (on a machine without a GPU use_fp16 is forced off, so it is inert there)."""
         super().__init__()
         if use_bf16 and use_fp16:                                     # modeling.py:443-444
             raise ValueError("Cannot use fp16 and bf16 in the same time!")
@@ -292,6 +297,8 @@ class ModelForInference(nn.Module):
             self.model.native_f32 = True
         if f32_attention and hasattr(self.model, "f32_attention"):
             self.model.f32_attention = True
+        if native_fp16 and hasattr(self.model, "native_fp16"):
+            self.model.native_fp16 = True
 
     @torch.inference_mode()
     def encode(

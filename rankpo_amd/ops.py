@@ -537,7 +537,33 @@ def swiglu_down(gu, weight, last_in_block: bool = False):
     return _SwiGLUDown.apply(gu, weight, bool(last_in_block))
 
 
+class fp16_native:
+    """Context of a packed no-grad pass of an fp16 LlamaEncoder that opted in to the fp16 row kernels (encoder.LLAMA_FP16_NATIVE /
+    LlamaEncoder.native_fp16): inside it, and only with grad mode off, `fused_encoder_ops_ok` / `fused_norm_ok` accept fp16 HIP
+    tensors, which sends RMSNorm, RoPE and SwiGLU to the fp16 forward instantiations of rpo_add_rmsnorm_fwd / rpo_rope /
+    rpo_swiglu_fwd (there are no fp16 backward entries).  Outside it an fp16 tensor is refused as before."""
+    _tls = threading.local()      # per thread, as `recomputing`
+
+    @staticmethod
+    def active():
+        return getattr(fp16_native._tls, "depth", 0) > 0
+
+    def __enter__(self):
+        fp16_native._tls.depth = getattr(fp16_native._tls, "depth", 0) + 1
+        return self
+
+    def __exit__(self, *exc):
+        fp16_native._tls.depth -= 1
+        return False
+
+
+def _fp16_rows_ok(x) -> bool:
+    return x.dtype == torch.float16 and x.is_cuda and fp16_native.active() and not torch.is_grad_enabled()
+
+
 def fused_encoder_ops_ok(x, head_dim=None) -> bool:
+    if _fp16_rows_ok(x):
+        return head_dim is None or (head_dim % 2 == 0 and (head_dim // 2) % 8 == 0)
     if not x.is_cuda or x.dtype not in (torch.float32, torch.bfloat16):
         return False
     v = 8 if x.dtype == torch.bfloat16 else 4
@@ -601,6 +627,8 @@ def add_rmsnorm(x, delta, weight, eps):
 
 
 def fused_norm_ok(x) -> bool:
+    if _fp16_rows_ok(x):
+        return x.shape[-1] % 8 == 0 and x.shape[-1] // 8 <= 64 * 8
     if not x.is_cuda or x.dtype not in (torch.float32, torch.bfloat16):
         return False
     v = 8 if x.dtype == torch.bfloat16 else 4
@@ -1299,6 +1327,57 @@ def causal_attn_f32(q, k, v, cu_q, cu_k, tiles, scale, want_lse: bool = False):
                                           cu_q.data_ptr(), cu_k.data_ptr(), tiles.data_ptr(), tiles.shape[0], tiles.shape[1],
                                           CAUSAL_ATTN_F32_Q_BLOCK, cu_q.numel() - 1, nh, k.shape[1], hd, float(scale),
                                           out.data_ptr(), nh * hd, _p(lse), _stream(q)), "rpo_causal_attn_fwd_f32")
+    return out, lse
+
+
+# ------------------------------------------------------------------------------------------------
+# (9e) causal fp16 attention of the packed Llama pass (LlamaEncoder.pooled_last_token_multi under no-grad, opt-in:
+# encoder.LLAMA_FP16_NATIVE; no autograd: forward only).  Header section (9e), rankpo_amd/csrc/causal_attn_f16.hip.
+# ------------------------------------------------------------------------------------------------
+CAUSAL_ATTN_F16_Q_BLOCK = CAUSAL_ATTN_F32_Q_BLOCK    # the kernel takes the 32-query entries of (9c): one list format
+CAUSAL_ATTN_F16_HEAD_DIMS = (64, 128)
+CAUSAL_ATTN_F16_GROUPS = (1, 2, 4, 8)
+causal_attn_f16_tile_list = causal_attn_f32_tile_list
+causal_attn_f16_tile_table = causal_attn_f32_tile_table
+
+
+def causal_attn_f16_shape_ok(num_heads: int, num_kv_heads: int, head_dim: int) -> bool:
+    return (head_dim in CAUSAL_ATTN_F16_HEAD_DIMS and num_kv_heads > 0 and num_heads % num_kv_heads == 0
+            and num_heads // num_kv_heads in CAUSAL_ATTN_F16_GROUPS)
+
+
+def causal_attn_f16_ok(q, k, v) -> bool:
+    """What rpo_causal_attn_fwd_f16 takes, restated: float16 on a HIP device, q [Tq, nh, hd] and k / v [Tk, nkv, hd] with heads
+    contiguous inside a token row, head_dim 64 or 128, nh / nkv in (1, 2, 4, 8), 16-byte aligned with token strides % 8 == 0."""
+    if not all(t.is_cuda and t.dtype == torch.float16 and t.dim() == 3 for t in (q, k, v)):
+        return False
+    hd = q.shape[2]
+    if k.shape != v.shape or k.shape[2] != hd or not causal_attn_f16_shape_ok(q.shape[1], k.shape[1], hd):
+        return False
+    return all(t.stride(2) == 1 and t.stride(1) == hd and t.stride(0) % 8 == 0 and t.stride(0) > 0 and t.data_ptr() % 16 == 0
+               for t in (q, k, v))
+
+
+def causal_attn_f16(q, k, v, cu_q, cu_k, tiles, scale, want_lse: bool = False):
+    """Causal grouped-query variable-length attention on fp16 storage: q [Tq, nh, hd], k / v [Tk, nkv, hd] (heads contiguous, token
+    stride free: column blocks of one fused projection output), cu_q / cu_k int32 [N + 1] on the device, tiles from
+    `causal_attn_f16_tile_table(lens_q, lens_k)` (which checks lens_q <= lens_k).  Query i of sequence n sees its keys
+    j <= i + (lk - lq).  Returns (out fp16 [Tq, nh * hd], lse f32 [nh, Tq] or None).  Forward only: no autograd node."""
+    if not causal_attn_f16_ok(q, k, v):
+        raise ValueError("causal_attn_f16: float16 HIP tensors [T, heads, head_dim] with head_dim in (64, 128), 1 / 2 / 4 / 8 query "
+                         "heads per kv head, heads contiguous, 16-byte aligned, token strides % 8 == 0")
+    if (cu_q.numel() != cu_k.numel() or cu_q.dtype != torch.int32 or cu_k.dtype != torch.int32 or tiles.dtype != torch.int32
+            or tiles.dim() != 2 or tiles.shape[1] != 2 or not tiles.is_contiguous()):
+        raise ValueError("causal_attn_f16: cu_q / cu_k int32 [N + 1], tiles int32 [n, 2]")
+    lib = _lib.load()
+    Tq, nh, hd = q.shape
+    out = torch.empty((Tq, nh * hd), dtype=q.dtype, device=q.device)
+    lse = torch.empty((nh, Tq), dtype=torch.float32, device=q.device) if want_lse else None
+    with torch.cuda.device(q.device):
+        check(lib.rpo_causal_attn_fwd_f16(q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(0), k.stride(0), v.stride(0),
+                                          cu_q.data_ptr(), cu_k.data_ptr(), tiles.data_ptr(), tiles.shape[0], tiles.shape[1],
+                                          CAUSAL_ATTN_F16_Q_BLOCK, cu_q.numel() - 1, nh, k.shape[1], hd, float(scale),
+                                          out.data_ptr(), nh * hd, _p(lse), _stream(q)), "rpo_causal_attn_fwd_f16")
     return out, lse
 
 
