@@ -537,6 +537,44 @@ int rpo_causal_attn_fwd_f16(const void* q, const void* k, const void* v, int64_t
                             int64_t head_dim, float scale, void* out, int64_t out_stride, float* lse, rpo_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * (9f) backward of the causal fp16 attention of (9e), for the packed fp16 Llama TRAINING pass
+ * (rankpo_amd/csrc/causal_attn_f16_bwd.hip; opt-in: encoder.LLAMA_FP16_NATIVE_TRAIN / LlamaEncoder.native_fp16_train,
+ * ModelForTraining(native_fp16=True)).  No allocation, no host sync, no atomics: deterministic.
+ *
+ * rpo_causal_attn_bwd_f16: the contract of (9d) on fp16 storage, in the argument order of rpo_causal_attn_bwd_f32 (no dtype
+ * argument).  ONE entry that launches the dQ kernel, then the dK/dV kernel, on the caller's stream.  q / k / v / out / dout /
+ * dq / dk / dv are fp16, token strides in fp16 ELEMENTS, heads contiguous; lse: f32 [num_heads][total_q], as
+ * rpo_causal_attn_fwd_f16 writes it (required); the visibility rule is j <= i + (lk - lq).  tiles / k_tiles: int32 [n][2], 32 rows
+ * per entry, the query and key lists of (9c) / (9d); tile_cols and q_block describe both.  q | k | v and dq | dk | dv may each be
+ * column blocks of one fused buffer.  ws: f32 workspace, required: the dQ kernel writes delta = dout . out per head and query
+ * there and the dK/dV kernel reads it, so num_heads * total_q floats suffice (half of what (9d) asks for; the signature is
+ * (9d)'s).
+ * Arithmetic: S, dP and the three gradient products run on v_mfma_f32_16x16x32_f16 with f32 accumulation; raw scores stay f32
+ * (never fp16): each 32-wide chunk of the head dim is one MFMA summed from zero and the chunks' f32 sums are added without a
+ * rounding, the score carried as an f32 pair into the exponent;
+ * p = exp2((s * scale - lse) * log2(e)) with log2(e) carried as hi + lo, as in (9e); no renormalisation by the sum of p (one f32
+ * lse at |lse| ~ 60 carries ~4e-6 relative into p, two orders below fp16's 2^-11).  P is rounded to fp16 exactly once, as the
+ * operand of dV; dS = p (dP - delta) is formed in f32 and rounded to fp16 exactly once, as the operand of dQ and dK; scale is
+ * applied in f32; dq / dk / dv are rounded to fp16 once (overflow gives inf, never a saturated value).  A non-finite dout
+ * element reaches the dq row of its query.
+ * Summation order: dq[i] sums the keys ascending in 32-key steps; dk[j] / dv[j] sum (query step of 32, query head of the group)
+ * ascending from the first query that sees the first key of j's 32-key entry, each (step, head) summed from zero and then added
+ * to the running total: the indices alone fix the order, so results are bit-reproducible and do not depend on what else is packed.
+ * Zero fill: every dq row of a listed entry and every dk / dv row of a listed key entry is written; keys no query sees (lq == 0)
+ * get exact zeros; a query whose lse is -inf contributes exact zeros, never NaN.  No access leaves a sequence (row loads are
+ * clamped as in the forward).
+ * head_dim 64 or 128; num_heads / num_kv_heads in {1, 2, 4, 8}; tile_cols == 2, q_block == 32; q / k / v / out / dout / dq / dk /
+ * dv 16-byte aligned with token strides % 8 == 0: anything else is RPO_ERR_UNSUPPORTED before any launch.  ntiles == 0 and
+ * nktiles == 0 is RPO_OK and launches nothing; an empty list alone skips its kernel.
+ * --------------------------------------------------------------------------------------------- */
+int rpo_causal_attn_bwd_f16(const void* q, const void* k, const void* v, const void* out, const void* dout, int64_t q_stride,
+                            int64_t k_stride, int64_t v_stride, int64_t out_stride, int64_t dout_stride, const float* lse,
+                            const int* cu_seqlens_q, const int* cu_seqlens_k, const int* tiles, int64_t ntiles, const int* k_tiles,
+                            int64_t nktiles, int64_t tile_cols, int64_t q_block, int64_t num_seqs, int64_t num_heads,
+                            int64_t num_kv_heads, int64_t head_dim, float scale, void* dq, int64_t dq_stride, void* dk,
+                            int64_t dk_stride, void* dv, int64_t dv_stride, float* ws, rpo_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * (10) packed TRAINING step of the BERT / XLM-R block (rankpo_amd/csrc/bert_ops.hip; BertEncoder.pooled_cls_train, used by
  * ModelForTraining.embed for CLS-pooled models).  bf16 or fp16 storage (RPO_DT_F32 is RPO_ERR_UNSUPPORTED), f32 arithmetic,
  * no allocation, no host sync, no atomics: deterministic.  Shapes, strides, work lists and alignment as in section (9) unless

@@ -131,6 +131,7 @@ SIGNATURES = {
     "rpo_embed_grad_sorted": (C.c_int, [_vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp,
                                         _i64, _vp]),
 }
+SIGNATURES["rpo_causal_attn_bwd_f16"] = SIGNATURES["rpo_causal_attn_bwd_f32"]   # one argument list: the very row
 
 _lib = None
 

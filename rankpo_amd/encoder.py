@@ -222,6 +222,15 @@ LLAMA_FP16_NATIVE = False  # True: a float16 LlamaEncoder runs its packed no-gra
 #                            `LlamaEncoder.native_fp16` / ModelForInference(native_fp16=True) is the same switch for one model.
 #                            Forward only: under grad mode, on f32 / bf16 storage, on the CPU, for head dims or group sizes the
 #                            kernel refuses, or off the packed path (left-padded batches) nothing changes.
+LLAMA_FP16_NATIVE_TRAIN = False  # True: a float16 LlamaEncoder runs the attention of its packed pass UNDER GRAD MODE on
+#                                  `ops.causal_attn_f16_train` (the forward kernel above with lse, and its backward
+#                                  causal_attn_f16_bwd.hip: dQ and dK/dV on the fp16 MFMA, deterministic; one forward and one
+#                                  backward call per block) instead of `aten._flash_attention_forward` differentiated by
+#                                  PyTorch's flash backward.  `LlamaEncoder.native_fp16_train` / ModelForTraining(native_fp16=True)
+#                                  is the same switch for one model.  Attention only: RMSNorm, RoPE and SwiGLU stay what they are
+#                                  under grad mode (the pass does not enter `ops.fp16_native`).  Under no-grad, on f32 / bf16
+#                                  storage, on the CPU, for shapes the kernel refuses or off the packed path nothing changes;
+#                                  LLAMA_FP16_NATIVE stays "no-grad only".
 FWD128_ONE_WAVE = True   # head_dim 128 with 4 (8, ..) q heads per kv head: the forward walks its own list (64 queries x 4 heads per entry)
 #                          with the one-wave-per-SIMD kernel (ops.FWD_ONE_WAVE_HEAD_DIMS names the head dims); False: the 128-query kernel
 #                          of rounds 3-4 (the A/B arm of `bench.py --fwd128 classic`)
@@ -243,8 +252,12 @@ class VarlenCtx:
     opted in, the same two query lists and the key lists of `ops.causal_attn_f32_train` beside them (`f32_k_tiles`,
     `f32_last_k_tiles`; else None), which is what sends the attention there; the work lists of `ops.causal_attn_f16` where the
     native fp16 pass was opted in (else None): `f16_tiles` (lens, lens) and `f16_last_tiles` ([1] * N, lens) -- attributes that
-    `pooled_last_token_multi` sets on the object (tests/test_llama_f32_train_host.py pins the constructor's parameter list)."""
+    `pooled_last_token_multi` sets on the object (tests/test_llama_f32_train_host.py pins the constructor's parameter list);
+    under grad mode with the fp16 TRAINING attention opted in, the same two query lists and the key lists of
+    `ops.causal_attn_f16_train` beside them (`f16_k_tiles`, `f16_last_k_tiles`; else None), attributes as well, which is what
+    sends the attention there."""
     f16_tiles = f16_last_tiles = None
+    f16_k_tiles = f16_last_k_tiles = None
 
     def __init__(self, cu, lens, max_len, tiles=None, k_tiles=None, fwd_tiles=None, f32_tiles=None, f32_last_tiles=None,
                  f32_k_tiles=None, f32_last_k_tiles=None):
@@ -274,6 +287,12 @@ def _varlen_causal_attention(q, k, v, ctx: VarlenCtx):
             and _ops.causal_attn_f16_ok(q, k, v)):
         # fp16 storage, opted in (LLAMA_FP16_NATIVE / native_fp16), no-grad: one launch of the fp16-MFMA kernel for the batch
         return _ops.causal_attn_f16(q, k, v, ctx.cu, ctx.cu, ctx.f16_tiles, 1.0 / math.sqrt(q.shape[-1]))[0].view(q.shape)
+    if (ctx.f16_k_tiles is not None and q.dtype == torch.float16 and torch.is_grad_enabled()
+            and _ops.causal_attn_f16_ok(q, k, v)):
+        # fp16 storage, opted in (LLAMA_FP16_NATIVE_TRAIN / native_fp16_train), grad mode: the same kernel with lse, and its
+        # backward as ONE autograd node
+        return _ops.causal_attn_f16_train(q, k, v, ctx.cu, ctx.cu, ctx.f16_tiles, ctx.f16_k_tiles,
+                                          1.0 / math.sqrt(q.shape[-1])).view(q.shape)
     if q.is_cuda and q.dtype in (torch.bfloat16, torch.float16):
         return torch.ops.aten._flash_attention_forward(q, k, v, ctx.cu, ctx.cu, ctx.max_len, ctx.max_len, 0.0, True,
                                                        False)[0]
@@ -304,6 +323,12 @@ def _varlen_last_query_attention(q, k, v, ctx: VarlenCtx):
         # the same fp16 kernel with one query per sequence: bottom-right aligned, so that query sees every key
         cu_q = torch.arange(N + 1, device=q.device, dtype=torch.int32)
         return _ops.causal_attn_f16(q, k, v, cu_q, ctx.cu, ctx.f16_last_tiles, 1.0 / math.sqrt(q.shape[-1]))[0].view(q.shape)
+    if (ctx.f16_last_k_tiles is not None and q.dtype == torch.float16 and torch.is_grad_enabled()
+            and _ops.causal_attn_f16_ok(q, k, v)):
+        # grad mode, opted in (LLAMA_FP16_NATIVE_TRAIN / native_fp16_train): the one-query form of the same autograd node
+        cu_q = torch.arange(N + 1, device=q.device, dtype=torch.int32)
+        return _ops.causal_attn_f16_train(q, k, v, cu_q, ctx.cu, ctx.f16_last_tiles, ctx.f16_last_k_tiles,
+                                          1.0 / math.sqrt(q.shape[-1])).view(q.shape)
     if q.is_cuda and q.dtype in (torch.bfloat16, torch.float16):
         cu_q = torch.arange(N + 1, device=q.device, dtype=torch.int32)
         return torch.ops.aten._flash_attention_forward(q, k, v, cu_q, ctx.cu, 1, ctx.max_len, 0.0, False, False)[0]
@@ -553,6 +578,7 @@ class LlamaEncoder(nn.Module):
         self.f32_attention = False         # True: as LLAMA_F32_ATTENTION, for this model (float32 storage, no-grad packed pass)
         self.f32_attention_train = False   # True: as LLAMA_F32_ATTENTION_TRAIN, for this model (float32 storage, grad mode)
         self.native_fp16 = False           # True: as LLAMA_FP16_NATIVE, for this model (float16 storage, no-grad packed pass)
+        self.native_fp16_train = False     # True: as LLAMA_FP16_NATIVE_TRAIN, for this model (float16 storage, grad mode)
         self.apply(self._init)
 
     def _init(self, m):
@@ -775,6 +801,16 @@ class LlamaEncoder(nn.Module):
             f16_last_tiles = _ops.causal_attn_f16_tile_table([1] * N, lens, x.device)
         ctx = VarlenCtx(cu, lens, max(lens), tiles, k_tiles, fwd_tiles, f32_tiles, f32_last_tiles, f32_k_tiles=f32_k_tiles,
                         f32_last_k_tiles=f32_last_k_tiles)
+        if ((LLAMA_FP16_NATIVE_TRAIN or self.native_fp16_train) and x.is_cuda and x.dtype == torch.float16
+                and torch.is_grad_enabled()
+                and _ops.causal_attn_f16_shape_ok(self.config.num_attention_heads, self.config.num_key_value_heads,
+                                                  self.config.head_dim)):
+            # opted in, grad mode: the two query lists and the key lists of ops.causal_attn_f16_train; attention only -- the pass
+            # does not enter ops.fp16_native (the row kernels have no fp16 backward)
+            ctx.f16_tiles = _ops.causal_attn_f16_tile_table(lens, lens, x.device)
+            ctx.f16_last_tiles = _ops.causal_attn_f16_tile_table([1] * N, lens, x.device)
+            ctx.f16_k_tiles = _ops.causal_attn_f16_key_tile_table(lens, lens, x.device)
+            ctx.f16_last_k_tiles = _ops.causal_attn_f16_key_tile_table([1] * N, lens, x.device)
         if f16_tiles is not None:
             ctx.f16_tiles, ctx.f16_last_tiles = f16_tiles, f16_last_tiles
             with _ops.fp16_native():

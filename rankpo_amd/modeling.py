@@ -84,11 +84,17 @@ class ModelForTraining(nn.Module):
         torch_dtype=None,
         unpad: bool = True,
         f32_attention: bool = False,
+        native_fp16: bool = False,
     ):
         """f32_attention: a float32 Llama encoder runs the attention of its packed pass on the hand-written f32-MFMA kernels, under
         grad mode (`LlamaEncoder.f32_attention_train`, `ops.causal_attn_f32_train`: forward and backward, one call each per
         block) and under no-grad (`LlamaEncoder.f32_attention`: eval-mode scoring), instead of one SDPA call per sequence; off by
-        default, and without effect on 16-bit models and BERT-family encoders."""
+        default, and without effect on 16-bit models and BERT-family encoders.
+        native_fp16: a float16 Llama encoder runs the attention of its packed pass under grad mode on the hand-written fp16-MFMA
+        kernels (`LlamaEncoder.native_fp16_train`, `ops.causal_attn_f16_train`: forward and backward, one call each per block)
+        instead of PyTorch's flash forward and backward, and its no-grad pass (eval-mode scoring) as
+        ModelForInference(native_fp16=True) does (`LlamaEncoder.native_fp16`); off by default, and without effect on models that
+        are not float16 and on BERT-family encoders."""
         super().__init__()
         self.unpad = unpad
         # attn_implementation / use_cache / cache_dir / token / trust_remote_code are accepted for signature
@@ -97,6 +103,9 @@ class ModelForTraining(nn.Module):
         if f32_attention and hasattr(self.model, "f32_attention_train"):
             self.model.f32_attention = True
             self.model.f32_attention_train = True
+        if native_fp16 and hasattr(self.model, "native_fp16_train"):
+            self.model.native_fp16 = True
+            self.model.native_fp16_train = True
         self.criterion = nn.CrossEntropyLoss(reduction="mean")     # kept for attribute parity (modeling.py:179)
 
         self.normalize_embeddings = normalize_embeddings

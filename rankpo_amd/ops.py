@@ -1475,6 +1475,84 @@ def causal_attn_f32_train(q, k, v, cu_q, cu_k, tiles, k_tiles, scale):
     return _CausalAttnF32Train.apply(q, k, v, cu_q, cu_k, tiles, k_tiles, scale)
 
 
+# ------------------------------------------------------------------------------------------------
+# (9f) the backward of (9e) and the autograd Function over the pair: the attention of the packed fp16 Llama TRAINING pass
+# (opt-in: encoder.LLAMA_FP16_NATIVE_TRAIN).  Header section (9f), rankpo_amd/csrc/causal_attn_f16_bwd.hip.
+# ------------------------------------------------------------------------------------------------
+causal_attn_f16_key_tile_list = causal_attn_f32_key_tile_list      # the 32-key entries of (9d): one list format
+causal_attn_f16_key_tile_table = causal_attn_f32_key_tile_table
+
+
+def causal_attn_f16_bwd(q, k, v, out, lse, dout, cu_q, cu_k, tiles, k_tiles, scale):
+    """The gradients of `causal_attn_f16`: (dq [Tq, nh, hd], dk [Tk, nkv, hd], dv [Tk, nkv, hd]), float16, column blocks of ONE
+    fused [T, (nh + 2 nkv) hd] buffer where Tq == Tk, from its inputs, its results (out fp16 [Tq, nh * hd], lse f32 [nh, Tq]) and
+    dout (the shape of out or of q).  tiles as the forward's, k_tiles from `causal_attn_f16_key_tile_table` on the same lengths.
+    One entry, two launches (dQ, then dK/dV), no atomics: deterministic, and independent of what else is packed in the batch.
+    The raw op: no autograd node."""
+    if not causal_attn_f16_ok(q, k, v):
+        raise ValueError("causal_attn_f16_bwd: float16 HIP tensors [T, heads, head_dim] with head_dim in (64, 128), 1 / 2 / 4 / 8 "
+                         "query heads per kv head, heads contiguous, 16-byte aligned, token strides % 8 == 0")
+    if (cu_q.numel() != cu_k.numel() or cu_q.dtype != torch.int32 or cu_k.dtype != torch.int32 or tiles.dtype != torch.int32
+            or k_tiles.dtype != torch.int32 or tiles.dim() != 2 or k_tiles.dim() != 2 or tiles.shape[1] != 2
+            or k_tiles.shape[1] != 2 or not tiles.is_contiguous() or not k_tiles.is_contiguous()):
+        raise ValueError("causal_attn_f16_bwd: cu_q / cu_k int32 [N + 1], tiles / k_tiles int32 [n, 2]")
+    Tq, nh, hd = q.shape
+    Tk, nkv, _ = k.shape
+    if (out.dtype != torch.float16 or dout.dtype != torch.float16 or lse.dtype != torch.float32 or out.numel() != q.numel()
+            or dout.numel() != q.numel() or lse.shape != (nh, Tq) or not lse.is_contiguous()):
+        raise ValueError("causal_attn_f16_bwd: out / dout float16 [Tq, nh * hd], lse float32 [nh, Tq] contiguous")
+
+    def rows(t):       # [Tq, nh * hd] with contiguous rows, 16-byte aligned, token stride % 8 == 0: as it is, else a copy
+        t = t.reshape(Tq, nh * hd)                      # a view wherever the strides allow one
+        if t.stride(1) != 1 or t.stride(0) % 8 or t.stride(0) <= 0 or t.data_ptr() % 16:
+            t = t.contiguous()
+        return t
+    out, dout = rows(out), rows(dout)
+    lib = _lib.load()
+    if Tq == Tk:       # self-attention: one fused gradient buffer, as the q|k|v projection output lies
+        fused = torch.empty((Tq, (nh + 2 * nkv) * hd), dtype=torch.float16, device=q.device)
+        dq = fused[:, :nh * hd].view(Tq, nh, hd)
+        dk = fused[:, nh * hd:(nh + nkv) * hd].view(Tk, nkv, hd)
+        dv = fused[:, (nh + nkv) * hd:].view(Tk, nkv, hd)
+    else:
+        dq = torch.empty((Tq, nh, hd), dtype=torch.float16, device=q.device)
+        fused = torch.empty((Tk, 2 * nkv * hd), dtype=torch.float16, device=q.device)
+        dk = fused[:, :nkv * hd].view(Tk, nkv, hd)
+        dv = fused[:, nkv * hd:].view(Tk, nkv, hd)
+    ws = torch.empty((nh, Tq), dtype=torch.float32, device=q.device)
+    with torch.cuda.device(q.device):
+        check(lib.rpo_causal_attn_bwd_f16(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(), q.stride(0),
+                                          k.stride(0), v.stride(0), out.stride(0), dout.stride(0), lse.data_ptr(), cu_q.data_ptr(),
+                                          cu_k.data_ptr(), tiles.data_ptr(), tiles.shape[0], k_tiles.data_ptr(), k_tiles.shape[0],
+                                          tiles.shape[1], CAUSAL_ATTN_F16_Q_BLOCK, cu_q.numel() - 1, nh, nkv, hd, float(scale),
+                                          dq.data_ptr(), dq.stride(0), dk.data_ptr(), dk.stride(0), dv.data_ptr(), dv.stride(0),
+                                          ws.data_ptr(), _stream(q)), "rpo_causal_attn_bwd_f16")
+    return dq, dk, dv
+
+
+class _CausalAttnF16Train(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, cu_q, cu_k, tiles, k_tiles, scale):
+        out, lse = causal_attn_f16(q, k, v, cu_q, cu_k, tiles, scale, want_lse=True)
+        ctx.save_for_backward(q, k, v, out, lse, cu_q, cu_k, tiles, k_tiles)
+        ctx.scale = scale
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse, cu_q, cu_k, tiles, k_tiles = ctx.saved_tensors
+        dq, dk, dv = causal_attn_f16_bwd(q, k, v, out, lse, dout, cu_q, cu_k, tiles, k_tiles, ctx.scale)
+        return dq, dk, dv, None, None, None, None, None
+
+
+def causal_attn_f16_train(q, k, v, cu_q, cu_k, tiles, k_tiles, scale):
+    """`causal_attn_f16` with a gradient: an autograd Function over (q, k, v), column-block views of the fused projection output
+    included.  Forward: `causal_attn_f16(..., want_lse=True)` (the same deterministic kernel, also when a checkpointed block
+    recomputes it); saved: q, k, v, out, lse and the lists; backward: ONE call of `causal_attn_f16_bwd` (dout of any stride: made
+    contiguous only if needed).  Returns out fp16 [Tq, nh * hd]."""
+    return _CausalAttnF16Train.apply(q, k, v, cu_q, cu_k, tiles, k_tiles, scale)
+
+
 def add_layernorm(a, b, weight, bias, eps, out=None):
     """LayerNorm(a + b) * weight + bias over the last dim of 2-D row-strided a / b (b may be None); a + b rounded to the storage
     dtype first.  out: [rows, d] (row stride free) or None (a new contiguous tensor)."""
