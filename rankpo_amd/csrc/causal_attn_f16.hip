@@ -21,9 +21,9 @@
 // (sign-adjusted by negating Q, exact in fp16, when scale < 0): p = exp2(((s - m) |scale|) log2 e) with log2 e carried as hi + lo,
 // as in the f32 kernel.  Q is never pre-scaled.  The row sum adds the ROUNDED p that multiplies V (the bf16 kernels' convention);
 // O is divided in f32 and rounded to fp16 once (overflow -> inf, as torch's .half()).
-// Causal rule, bottom-right aligned: query i of a sequence sees key j iff j <= i + (lk - lq).  The key loop of a block ends with
-// the step that holds the last visible key of its last query; inside a step masked keys get p = 0 and do not enter the running
-// maximum (a query with no visible key in a step keeps its maximum: alpha = 1).  Key 0 is visible to every query (lq <= lk, the
+// The work-list decode with its guard, the causal rule (bottom-right aligned: query i sees key j iff j <= i + (lk - lq); where a
+// block's key loop ends) and the running-maximum step live in causal_attn_common.hpp, with the entry's checks and dispatch.  Inside
+// a step masked keys get p = 0 and do not enter the running maximum (no visible key in a step: the maximum stays, alpha = 1).  Key 0 is visible to every query (lq <= lk, the
 // caller's precondition), so the maximum is finite from the first step on; with lq > lk the rows that see no key come out as zeros
 // with lse = -inf.  Rows are clamped to the sequence on every load: no access leaves it.
 // Budget (the .vgpr_count of `make isa-llama-f16`, no scratch in any instantiation):
@@ -33,15 +33,13 @@
 //   head_dim 128 (1 / 1 / 2 / 3): what hipcc takes unasked, no waves-per-SIMD attribute.
 //   LDS: 32 x (HD + 8) x 2 (K rows) + HD x 40 x 2 (V^T) = 9 728 bytes (head_dim 64) / 18 944 (head_dim 128) per block.
 // Plain HIP with MFMA builtins; no assembly statements, no counted waits, no atomics: deterministic.
-#include "common.hpp"
+#include "causal_attn_common.hpp"
+
+using namespace causal_attn;
 
 namespace {
 
-constexpr int kQBlock = 32;         // queries per work-list entry
-constexpr int kKeys = 32;           // keys per step
 constexpr int kVtLd = kKeys + 8;    // row stride of the transposed V tile (elements): rows stay 16-byte aligned, 20 words apart
-constexpr float kLog2eHi = 1.44269502162933349609375f;        // (float)log2(e)
-constexpr float kLog2eLo = 1.92596299112661746e-8f;           // log2(e) - kLog2eHi
 
 __device__ __forceinline__ void mma_f16(uint4_t a, uint4_t b, float4_t& c) {
     c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_t, a), __builtin_bit_cast(half8_t, b), c, 0, 0, 0);
@@ -64,16 +62,12 @@ __global__ __launch_bounds__(64 * G) void causal_attn_fwd_f16_kernel(
     __shared__ __attribute__((aligned(16))) unsigned short ks[kKeys * KLD];
     __shared__ __attribute__((aligned(16))) unsigned short vt[HD * kVtLd];
 
-    const int entry = blockIdx.x, kvh = blockIdx.y;
-    const int seq = tiles[2 * entry], q0 = tiles[2 * entry + 1];
-    if (seq < 0 || seq >= num_seqs || q0 < 0) return;    // block-uniform
-    const int tq0 = cu_q[seq], lq = cu_q[seq + 1] - tq0;
-    const int tk0 = cu_k[seq], lk = cu_k[seq + 1] - tk0;
-    if (lq <= 0 || lk <= 0 || q0 >= lq) return;          // block-uniform
+    Entry ent;
+    if (!entry_listed(tiles, num_seqs, ent) || !query_entry_has_work(cu_q, cu_k, ent)) return;   // block-uniform
+    const int kvh = blockIdx.y, q0 = ent.row0, tq0 = ent.tq0, lq = ent.lq, tk0 = ent.tk0, lk = ent.lk;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 15, g = lane >> 4;
     const int h = kvh * G + w;
-    const int shift = lk - lq;                           // query i sees keys <= i + shift
-    const int kend = min(lk, min(q0 + kQBlock, lq) + shift);   // one past the last key any query of the entry sees
+    const int kend = key_loop_end(ent, q0, kQBlock);       // one past the last key any query of the entry sees
     const int64_t qcol = (int64_t)h * HD, kvcol = (int64_t)kvh * HD;
 
     uint4_t qf[QS][KS];
@@ -81,7 +75,7 @@ __global__ __launch_bounds__(64 * G) void causal_attn_fwd_f16_kernel(
 #pragma unroll
     for (int s = 0; s < QS; ++s) {
         const int qi = min(q0 + s * 16 + r, lq - 1);     // rows past the end: loaded (in bounds), never stored
-        lim[s] = qi + shift;
+        lim[s] = last_visible_key(ent, qi);
         const f16_t* qp = q + (int64_t)(tq0 + qi) * q_stride + qcol + 8 * g;
 #pragma unroll
         for (int c = 0; c < KS; ++c) {
@@ -152,19 +146,9 @@ __global__ __launch_bounds__(64 * G) void causal_attn_fwd_f16_kernel(
         uint4_t pf[QS];
 #pragma unroll
         for (int s = 0; s < QS; ++s) {
-            const int vis = lim[s] - kt - 4 * g;           // key 16 b + i of this lane is visible iff 16 b + i <= vis
-            float mx = -INFINITY;
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (16 * b + i <= vis) mx = fmaxf(mx, sc[b][s][i]);
-            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            const float mn = fmaxf(mrun[s], mx);           // finite from the first step on: key 0 is visible to every query
-            const float da = (mrun[s] - mn) * scale_abs;
-            const float alpha = mrun[s] == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(fmaf(da, kLog2eHi, da * kLog2eLo));
-            mrun[s] = mn;
+            const int vis = step_visibility(lim[s], kt, g);
+            const float alpha = running_max_step(sc[0][s], sc[1][s], vis, scale_abs, mrun[s]);
+            const float mn = mrun[s];
             float ps = 0.f;
             unsigned wd[4];
 #pragma unroll
@@ -172,8 +156,7 @@ __global__ __launch_bounds__(64 * G) void causal_attn_fwd_f16_kernel(
                 unsigned short pb[4];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const float dx = (sc[b][s][i] - mn) * scale_abs;
-                    const float p = (16 * b + i <= vis) ? __builtin_amdgcn_exp2f(fmaf(dx, kLog2eHi, dx * kLog2eLo)) : 0.f;
+                    const float p = key_visible(b, i, vis) ? exp_hilo((sc[b][s][i] - mn) * scale_abs) : 0.f;
                     const f16_t ph = (f16_t)p;             // the ONE rounding of P: the PV operand, and what the row sum adds
                     pb[i] = __builtin_bit_cast(unsigned short, ph);
                     ps += (float)ph;
@@ -216,13 +199,11 @@ __global__ __launch_bounds__(64 * G) void causal_attn_fwd_f16_kernel(
 }
 
 template <int HD, int G>
-void launch(const void* q, const void* k, const void* v, int64_t q_stride, int64_t k_stride, int64_t v_stride, const int* cu_q,
-            const int* cu_k, const int* tiles, int64_t ntiles, int64_t num_seqs, int64_t num_kv_heads, float scale, void* out,
-            int64_t out_stride, float* lse, hipStream_t st) {
-    const dim3 grid((unsigned)ntiles, (unsigned)num_kv_heads), block(64 * G);
-    RPO_LAUNCH((causal_attn_fwd_f16_kernel<HD, G>), grid, block, 0, st, (const f16_t*)q, (const f16_t*)k, (const f16_t*)v, q_stride,
-               k_stride, v_stride, cu_q, cu_k, tiles, (int)num_seqs, fabsf(scale), scale < 0.f ? 0x80008000u : 0u, (f16_t*)out,
-               out_stride, lse);
+void launch(const HostArgs& a, hipStream_t st) {
+    const dim3 grid((unsigned)a.ntiles, (unsigned)a.num_kv_heads), block(64 * G);
+    RPO_LAUNCH((causal_attn_fwd_f16_kernel<HD, G>), grid, block, 0, st, (const f16_t*)a.q, (const f16_t*)a.k, (const f16_t*)a.v,
+               a.q_stride, a.k_stride, a.v_stride, a.cu_q, a.cu_k, a.tiles, (int)a.num_seqs, fabsf(a.scale),
+               a.scale < 0.f ? 0x80008000u : 0u, (f16_t*)a.out, a.out_stride, a.lse);
 }
 
 }  // namespace
@@ -232,33 +213,14 @@ extern "C" int rpo_causal_attn_fwd_f16(const void* q, const void* k, const void*
                                        int64_t ntiles, int64_t tile_cols, int64_t q_block, int64_t num_seqs, int64_t num_heads,
                                        int64_t num_kv_heads, int64_t head_dim, float scale, void* out, int64_t out_stride,
                                        float* lse, rpo_stream_t stream) {
-    if (!q || !k || !v || !cu_seqlens_q || !cu_seqlens_k || !tiles || !out || ntiles < 0 || num_seqs <= 0 ||
-        num_seqs >= 0x7fffffff || num_heads <= 0 || num_kv_heads <= 0 || head_dim <= 0 || q_stride <= 0 || k_stride <= 0 ||
-        v_stride <= 0 || out_stride <= 0 || !(fabsf(scale) <= 3.0e38f))
-        return RPO_ERR_INVALID_ARG;
-    if ((head_dim != 64 && head_dim != 128) || num_heads % num_kv_heads != 0 || tile_cols != 2 || q_block != kQBlock ||
-        ntiles > 0x7fffffff || num_kv_heads > 65535)
-        return RPO_ERR_UNSUPPORTED;
-    const int64_t group = num_heads / num_kv_heads;
-    if (group != 1 && group != 2 && group != 4 && group != 8) return RPO_ERR_UNSUPPORTED;
+    HostArgs a{};
+    a.q = q, a.k = k, a.v = v, a.q_stride = q_stride, a.k_stride = k_stride, a.v_stride = v_stride;
+    a.cu_q = cu_seqlens_q, a.cu_k = cu_seqlens_k, a.tiles = tiles, a.ntiles = ntiles, a.tile_cols = tile_cols, a.q_block = q_block;
+    a.num_seqs = num_seqs, a.num_heads = num_heads, a.num_kv_heads = num_kv_heads, a.head_dim = head_dim, a.scale = scale;
+    a.out = out, a.out_stride = out_stride, a.lse = lse;
     // 16-byte vector loads of q / k / v rows, 8-byte stores of out: 8-element (16-byte) token strides
-    if (!rpo_aligned16(q) || !rpo_aligned16(k) || !rpo_aligned16(v) || !rpo_aligned16(out) || q_stride % 8 || k_stride % 8 ||
-        v_stride % 8 || out_stride % 8 || (lse && (reinterpret_cast<uintptr_t>(lse) & 3)))
-        return RPO_ERR_UNSUPPORTED;
+    if (const int rc = check_forward(a, 8)) return rc;
     if (ntiles == 0) return RPO_OK;
-    hipStream_t st = (hipStream_t)stream;
-#define RPO_CAUSAL_F16_CASE(HD, G)                                                                                             \
-    if (head_dim == HD && group == G)                                                                                          \
-        launch<HD, G>(q, k, v, q_stride, k_stride, v_stride, cu_seqlens_q, cu_seqlens_k, tiles, ntiles, num_seqs, num_kv_heads, \
-                      scale, out, out_stride, lse, st);
-    RPO_CAUSAL_F16_CASE(64, 1)
-    RPO_CAUSAL_F16_CASE(64, 2)
-    RPO_CAUSAL_F16_CASE(64, 4)
-    RPO_CAUSAL_F16_CASE(64, 8)
-    RPO_CAUSAL_F16_CASE(128, 1)
-    RPO_CAUSAL_F16_CASE(128, 2)
-    RPO_CAUSAL_F16_CASE(128, 4)
-    RPO_CAUSAL_F16_CASE(128, 8)
-#undef RPO_CAUSAL_F16_CASE
+    RPO_CAUSAL_ATTN_DISPATCH(launch, a, (hipStream_t)stream)
     return rpo_launch_status();
 }

@@ -15,9 +15,9 @@
 //   (e = 0 / 1) per score block, added at the end.
 //   O^T = V^T P^T: MFMA t of a 16-key half takes p[t] as B as it lies in the accumulator (k slot g = key 4 g + t) and
 //   A = V[key 4 g + t][16 b + r] by ds_read_b32 (lane groups g, g + 1 read rows 4 apart = banks 16 apart: conflict-free).
-// Causal rule, bottom-right aligned: query i of a sequence sees key j iff j <= i + (lk - lq).  The key loop of a block ends with
-// the step that holds the last visible key of its last query; inside a step masked keys get p = 0 and do not enter the running
-// maximum (a query with no visible key in a step keeps its maximum: alpha = 1).  Key 0 is visible to every query (lq <= lk, the
+// The work-list decode with its guard, the causal rule (bottom-right aligned: query i sees key j iff j <= i + (lk - lq); where a
+// block's key loop ends) and the running-maximum step live in causal_attn_common.hpp, with the entry's checks and dispatch.  Inside
+// a step masked keys get p = 0 and do not enter the running maximum (no visible key in a step: the maximum stays, alpha = 1).  Key 0 is visible to every query (lq <= lk, the
 // caller's precondition), so the maximum is finite from the first step on; with lq > lk the rows that see no key come out as zeros
 // with lse = -inf, and no access leaves the sequence.
 // Budget (hipcc -Rpass-analysis=kernel-resource-usage, no scratch in any instantiation):
@@ -27,16 +27,13 @@
 //   head_dim 128 (1 / 1 / 2 / 2); see waves_per_simd below.
 //   LDS: 2 x 32 x (HD + 4) x 4 bytes = 17 408 (head_dim 64) / 33 792 (head_dim 128) per block.
 // Plain HIP with MFMA builtins; no asm statements, no counted waits, no atomics: deterministic.
-#include "common.hpp"
+#include "causal_attn_common.hpp"
+
+using namespace causal_attn;
 
 namespace {
 
 typedef __attribute__((ext_vector_type(2))) float float2_t;
-
-constexpr int kQBlock = 32;         // queries per work-list entry
-constexpr int kKeys = 32;           // keys per step
-constexpr float kLog2eHi = 1.44269502162933349609375f;        // (float)log2(e)
-constexpr float kLog2eLo = 1.92596299112661746e-8f;           // log2(e) - kLog2eHi
 
 // waves per SIMD the register allocation aims at: with 4 or 8 waves per block the staging registers are few and the kernel fits
 // 3 (head_dim 64) / 2 (head_dim 128) waves per SIMD without scratch, which hides one wave's softmax and barriers behind another's
@@ -58,15 +55,12 @@ __global__ __launch_bounds__(64 * G) __attribute__((amdgpu_waves_per_eu(waves_pe
     __shared__ __attribute__((aligned(16))) float ks[kKeys * LD];
     __shared__ __attribute__((aligned(16))) float vs[kKeys * LD];
 
-    const int entry = blockIdx.x, kvh = blockIdx.y;
-    const int seq = tiles[2 * entry], q0 = tiles[2 * entry + 1];
-    const int tq0 = cu_q[seq], lq = cu_q[seq + 1] - tq0;
-    const int tk0 = cu_k[seq], lk = cu_k[seq + 1] - tk0;
-    if (lq <= 0 || lk <= 0 || q0 >= lq) return;      // block-uniform
+    Entry ent;
+    if (!entry_listed(tiles, num_seqs, ent) || !query_entry_has_work(cu_q, cu_k, ent)) return;   // block-uniform
+    const int kvh = blockIdx.y, q0 = ent.row0, tq0 = ent.tq0, lq = ent.lq, tk0 = ent.tk0, lk = ent.lk;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 15, g = lane >> 4;
     const int h = kvh * G + w;
-    const int shift = lk - lq;                       // query i sees keys <= i + shift
-    const int kend = min(lk, min(q0 + kQBlock, lq) + shift);   // one past the last key any query of the entry sees
+    const int kend = key_loop_end(ent, q0, kQBlock);   // one past the last key any query of the entry sees
     const int64_t qcol = (int64_t)h * HD, kvcol = (int64_t)kvh * HD;
 
     float qf[QS][DK];
@@ -74,7 +68,7 @@ __global__ __launch_bounds__(64 * G) __attribute__((amdgpu_waves_per_eu(waves_pe
 #pragma unroll
     for (int s = 0; s < QS; ++s) {
         const int qi = min(q0 + s * 16 + r, lq - 1); // rows past the end: loaded (in bounds), never stored
-        lim[s] = qi + shift;
+        lim[s] = last_visible_key(ent, qi);
         const float* qp = q + (int64_t)(tq0 + qi) * q_stride + qcol + 2 * g;
 #pragma unroll
         for (int m = 0; m < DK / 2; ++m) {
@@ -145,26 +139,15 @@ __global__ __launch_bounds__(64 * G) __attribute__((amdgpu_waves_per_eu(waves_pe
         // online softmax; sc[b][s][i] = raw score of key kt + 16 b + 4 g + i, query q0 + 16 s + r; afterwards the probability
 #pragma unroll
         for (int s = 0; s < QS; ++s) {
-            const int vis = lim[s] - kt - 4 * g;           // key 16 b + i of this lane is visible iff 16 b + i <= vis
-            float mx = -INFINITY;
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (16 * b + i <= vis) mx = fmaxf(mx, sc[b][s][i]);
-            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            const float mn = fmaxf(mrun[s], mx);           // finite from the first step on: key 0 is visible to every query
-            const float da = (mrun[s] - mn) * scale_abs;
-            const float alpha = mrun[s] == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(fmaf(da, kLog2eHi, da * kLog2eLo));
-            mrun[s] = mn;
+            const int vis = step_visibility(lim[s], kt, g);
+            const float alpha = running_max_step(sc[0][s], sc[1][s], vis, scale_abs, mrun[s]);
+            const float mn = mrun[s];
             float ps = 0.f;
 #pragma unroll
             for (int b = 0; b < 2; ++b)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const float dx = (sc[b][s][i] - mn) * scale_abs;
-                    const float p = (16 * b + i <= vis) ? __builtin_amdgcn_exp2f(fmaf(dx, kLog2eHi, dx * kLog2eLo)) : 0.f;
+                    const float p = key_visible(b, i, vis) ? exp_hilo((sc[b][s][i] - mn) * scale_abs) : 0.f;
                     sc[b][s][i] = p;
                     ps += p;
                 }
@@ -201,13 +184,11 @@ __global__ __launch_bounds__(64 * G) __attribute__((amdgpu_waves_per_eu(waves_pe
 }
 
 template <int HD, int G>
-void launch(const void* q, const void* k, const void* v, int64_t q_stride, int64_t k_stride, int64_t v_stride, const int* cu_q,
-            const int* cu_k, const int* tiles, int64_t ntiles, int64_t num_seqs, int64_t num_kv_heads, float scale, void* out,
-            int64_t out_stride, float* lse, hipStream_t st) {
-    const dim3 grid((unsigned)ntiles, (unsigned)num_kv_heads), block(64 * G);
-    RPO_LAUNCH((causal_attn_fwd_f32_kernel<HD, G>), grid, block, 0, st, (const float*)q, (const float*)k, (const float*)v, q_stride,
-               k_stride, v_stride, cu_q, cu_k, tiles, (int)num_seqs, fabsf(scale), scale < 0.f ? -1.0f : 1.0f, (float*)out,
-               out_stride, lse);
+void launch(const HostArgs& a, hipStream_t st) {
+    const dim3 grid((unsigned)a.ntiles, (unsigned)a.num_kv_heads), block(64 * G);
+    RPO_LAUNCH((causal_attn_fwd_f32_kernel<HD, G>), grid, block, 0, st, (const float*)a.q, (const float*)a.k, (const float*)a.v,
+               a.q_stride, a.k_stride, a.v_stride, a.cu_q, a.cu_k, a.tiles, (int)a.num_seqs, fabsf(a.scale),
+               a.scale < 0.f ? -1.0f : 1.0f, (float*)a.out, a.out_stride, a.lse);
 }
 
 }  // namespace
@@ -217,32 +198,13 @@ extern "C" int rpo_causal_attn_fwd_f32(const void* q, const void* k, const void*
                                        int64_t ntiles, int64_t tile_cols, int64_t q_block, int64_t num_seqs, int64_t num_heads,
                                        int64_t num_kv_heads, int64_t head_dim, float scale, void* out, int64_t out_stride,
                                        float* lse, rpo_stream_t stream) {
-    if (!q || !k || !v || !cu_seqlens_q || !cu_seqlens_k || !tiles || !out || ntiles < 0 || num_seqs <= 0 ||
-        num_seqs >= 0x7fffffff || num_heads <= 0 || num_kv_heads <= 0 || head_dim <= 0 || q_stride <= 0 || k_stride <= 0 ||
-        v_stride <= 0 || out_stride <= 0 || !(fabsf(scale) <= 3.0e38f))
-        return RPO_ERR_INVALID_ARG;
-    if ((head_dim != 64 && head_dim != 128) || num_heads % num_kv_heads != 0 || tile_cols != 2 || q_block != kQBlock ||
-        ntiles > 0x7fffffff || num_kv_heads > 65535)
-        return RPO_ERR_UNSUPPORTED;
-    const int64_t group = num_heads / num_kv_heads;
-    if (group != 1 && group != 2 && group != 4 && group != 8) return RPO_ERR_UNSUPPORTED;
-    if (!rpo_aligned16(q) || !rpo_aligned16(k) || !rpo_aligned16(v) || !rpo_aligned16(out) || q_stride % 4 || k_stride % 4 ||
-        v_stride % 4 || out_stride % 4)
-        return RPO_ERR_UNSUPPORTED;
+    HostArgs a{};
+    a.q = q, a.k = k, a.v = v, a.q_stride = q_stride, a.k_stride = k_stride, a.v_stride = v_stride;
+    a.cu_q = cu_seqlens_q, a.cu_k = cu_seqlens_k, a.tiles = tiles, a.ntiles = ntiles, a.tile_cols = tile_cols, a.q_block = q_block;
+    a.num_seqs = num_seqs, a.num_heads = num_heads, a.num_kv_heads = num_kv_heads, a.head_dim = head_dim, a.scale = scale;
+    a.out = out, a.out_stride = out_stride, a.lse = lse;
+    if (const int rc = check_forward(a, 4)) return rc;       // 16-byte vectors of 4 floats
     if (ntiles == 0) return RPO_OK;
-    hipStream_t st = (hipStream_t)stream;
-#define RPO_CAUSAL_F32_CASE(HD, G)                                                                                             \
-    if (head_dim == HD && group == G)                                                                                          \
-        launch<HD, G>(q, k, v, q_stride, k_stride, v_stride, cu_seqlens_q, cu_seqlens_k, tiles, ntiles, num_seqs, num_kv_heads, \
-                      scale, out, out_stride, lse, st);
-    RPO_CAUSAL_F32_CASE(64, 1)
-    RPO_CAUSAL_F32_CASE(64, 2)
-    RPO_CAUSAL_F32_CASE(64, 4)
-    RPO_CAUSAL_F32_CASE(64, 8)
-    RPO_CAUSAL_F32_CASE(128, 1)
-    RPO_CAUSAL_F32_CASE(128, 2)
-    RPO_CAUSAL_F32_CASE(128, 4)
-    RPO_CAUSAL_F32_CASE(128, 8)
-#undef RPO_CAUSAL_F32_CASE
+    RPO_CAUSAL_ATTN_DISPATCH(launch, a, (hipStream_t)stream)
     return rpo_launch_status();
 }

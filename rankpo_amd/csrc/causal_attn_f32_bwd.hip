@@ -40,20 +40,16 @@
 //   dQ    head_dim 128: 462 / 420 / 392 / 201 registers, 1 / 1 / 1 / 2 waves per SIMD, 33 792 bytes
 //   dK/dV head_dim 64:  218 / 212 / 212 / 212 registers, 2 waves per SIMD, 17 408 bytes
 //   dK/dV head_dim 128: 370 / 350 / 350 / 350 registers, 1 wave per SIMD, 33 792 bytes
+// The decode of both work lists with its guard, the causal rule, exp through exp2 and the entry's checks and dispatch:
+// causal_attn_common.hpp.
 // Plain HIP with MFMA builtins; no asm statements, no counted waits, no atomics: deterministic.
-#include "common.hpp"
+#include "causal_attn_common.hpp"
+
+using namespace causal_attn;
 
 namespace {
 
 typedef __attribute__((ext_vector_type(2))) float float2_t;
-
-constexpr int kQBlock = 32;         // queries per query work-list entry = queries per step of the dK/dV kernel
-constexpr int kKeys = 32;           // keys per step of the dQ kernel = keys per key work-list entry
-constexpr float kLog2eHi = 1.44269502162933349609375f;        // (float)log2(e)
-constexpr float kLog2eLo = 1.92596299112661746e-8f;           // log2(e) - kLog2eHi
-
-// exp(x) through exp2 with log2(e) as hi + lo, as the forward takes it
-__device__ __forceinline__ float exp_hilo(float x) { return __builtin_amdgcn_exp2f(fmaf(x, kLog2eHi, x * kLog2eLo)); }
 
 // 16-query tiles a wave of the dQ kernel carries at once.  head_dim 128 takes one tile (Q^T, dO^T, dQ^T: 96 registers), not two,
 // where two would spill: with 8 waves per block (2 per SIMD: 256 registers each), and with 1 wave per block, which stages a
@@ -77,21 +73,18 @@ __global__ __launch_bounds__(64 * G) void causal_attn_bwd_dq_f32_kernel(
     __shared__ __attribute__((aligned(16))) float ks[kKeys * LD];
     __shared__ __attribute__((aligned(16))) float vs[kKeys * LD];
 
-    const int entry = blockIdx.x, kvh = blockIdx.y;
-    const int seq = tiles[2 * entry], q0e = tiles[2 * entry + 1];
-    const int tq0 = cu_q[seq], lq = cu_q[seq + 1] - tq0;
-    const int tk0 = cu_k[seq], lk = cu_k[seq + 1] - tk0;
-    if (lq <= 0 || lk <= 0 || q0e < 0 || q0e >= lq) return;   // block-uniform
+    Entry ent;
+    if (!entry_listed(tiles, num_seqs, ent) || !query_entry_has_work(cu_q, cu_k, ent)) return;   // block-uniform
+    const int kvh = blockIdx.y, q0e = ent.row0, tq0 = ent.tq0, lq = ent.lq, tk0 = ent.tk0, lk = ent.lk;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 15, g = lane >> 4;
     const int h = kvh * G + w;
-    const int shift = lk - lq;                       // query i sees keys <= i + shift
     const int64_t qcol = (int64_t)h * HD, kvcol = (int64_t)kvh * HD;
     const int64_t total_q = cu_q[num_seqs];
 
     for (int pass = 0; pass < PASSES; ++pass) {
         const int q0 = q0e + 16 * QS * pass;
         if (q0 >= lq) break;                         // block-uniform
-        const int kend = min(lk, min(q0 + 16 * QS, lq) + shift);   // one past the last key any query of the pass sees
+        const int kend = key_loop_end(ent, q0, 16 * QS);   // one past the last key any query of the pass sees
 
         float qf[QS][DK], dof[QS][DK], lsev[QS], delta[QS], lsum[QS];
         int lim[QS];                                 // last visible key of this lane's query
@@ -99,7 +92,7 @@ __global__ __launch_bounds__(64 * G) void causal_attn_bwd_dq_f32_kernel(
 #pragma unroll
         for (int s = 0; s < QS; ++s) {
             const int qi = min(q0 + s * 16 + r, lq - 1);   // rows past the end: loaded (in bounds), never stored
-            lim[s] = qi + shift;
+            lim[s] = last_visible_key(ent, qi);
             const float* qp = q + (int64_t)(tq0 + qi) * q_stride + qcol + 2 * g;
             const float* dp = dout + (int64_t)(tq0 + qi) * dout_stride + qcol + 2 * g;
             const float* op = out + (int64_t)(tq0 + qi) * out_stride + qcol + 2 * g;
@@ -195,13 +188,13 @@ __global__ __launch_bounds__(64 * G) void causal_attn_bwd_dq_f32_kernel(
             // p' and dS' = p' (dP - delta) in place of the scores; masked keys and rows without a finite lse: exact zeros
 #pragma unroll
             for (int s = 0; s < QS; ++s) {
-                const int vis = lim[s] - kt - 4 * g;           // key 16 b + i of this lane is visible iff 16 b + i <= vis
+                const int vis = step_visibility(lim[s], kt, g);
                 const bool ok = lsev[s] > -INFINITY;
 #pragma unroll
                 for (int b = 0; b < 2; ++b)
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        const float p = (ok && 16 * b + i <= vis) ? exp_hilo(fmaf(sc[b][s][i], scale_abs, -lsev[s])) : 0.f;
+                        const float p = (ok && key_visible(b, i, vis)) ? exp_hilo(fmaf(sc[b][s][i], scale_abs, -lsev[s])) : 0.f;
                         lsum[s] += p;
                         sc[b][s][i] = p * (dp[b][s][i] - delta[s]);
                     }
@@ -253,13 +246,10 @@ __global__ __launch_bounds__(128) void causal_attn_bwd_dkdv_f32_kernel(
     __shared__ __attribute__((aligned(16))) float qsm[kQBlock * LD];
     __shared__ __attribute__((aligned(16))) float dsm[kQBlock * LD];
 
-    const int entry = blockIdx.x, kvh = blockIdx.y;
-    const int seq = ktiles[2 * entry], k0 = ktiles[2 * entry + 1];
-    const int tq0 = cu_q[seq], lq = cu_q[seq + 1] - tq0;
-    const int tk0 = cu_k[seq], lk = cu_k[seq + 1] - tk0;
-    if (lk <= 0 || k0 < 0 || k0 >= lk) return;       // block-uniform
+    Entry ent;
+    if (!entry_listed(ktiles, num_seqs, ent) || !key_entry_has_work(cu_q, cu_k, ent)) return;   // block-uniform
+    const int kvh = blockIdx.y, k0 = ent.row0, tq0 = ent.tq0, lq = ent.lq, tk0 = ent.tk0, lk = ent.lk;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 15, g = lane >> 4;
-    const int shift = lk - lq;                       // query i sees keys <= i + shift
     const int kj = k0 + 16 * w + r;                  // this lane's key
     const int64_t kvcol = (int64_t)kvh * HD;
     const int64_t total_q = cu_q[num_seqs];
@@ -284,7 +274,7 @@ __global__ __launch_bounds__(128) void causal_attn_bwd_dkdv_f32_kernel(
     for (int b = 0; b < OB; ++b) dka[b] = dva[b] = float4_t{0.f, 0.f, 0.f, 0.f};
 
     // query steps of 32 from the first query that sees key k0 to the sequence's end; inside a step the G heads in ascending order
-    const int qbeg = max(0, k0 - shift);
+    const int qbeg = first_query_seeing(ent, k0);
     const int niter = lq > qbeg ? ((lq - qbeg + kQBlock - 1) / kQBlock) * G : 0;
 
     // the Q and dO rows of a (step, head) -> registers (rows clamped to the sequence: in bounds; queries past the end are masked)
@@ -366,7 +356,7 @@ __global__ __launch_bounds__(128) void causal_attn_bwd_dkdv_f32_kernel(
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int qi = qstep + 16 * s + 4 * g + i;
-                const bool on = qi < lq && kj <= qi + shift && lsev[s][i] > -INFINITY;
+                const bool on = qi < lq && kj <= last_visible_key(ent, qi) && lsev[s][i] > -INFINITY;
                 const float p = on ? exp_hilo(fmaf(sc[s][i], scale_abs, -lsev[s][i])) * st[s][i][1] : 0.f;
                 sc[s][i] = p;
                 dp[s][i] = p * (dp[s][i] - st[s][i][0]);
@@ -405,33 +395,21 @@ __global__ __launch_bounds__(128) void causal_attn_bwd_dkdv_f32_kernel(
     }
 }
 
-struct Args {
-    const float *q, *k, *v, *out, *dout;
-    int64_t q_stride, k_stride, v_stride, out_stride, dout_stride;
-    const float* lse;
-    const int *cu_q, *cu_k, *tiles, *k_tiles;
-    int64_t ntiles, nktiles, num_seqs, num_kv_heads;
-    float scale;
-    float *dq, *dk, *dv;
-    int64_t dq_stride, dk_stride, dv_stride;
-    float* ws;
-};
-
 template <int HD, int G>
-void launch(const Args& a, hipStream_t st) {
+void launch(const HostArgs& a, hipStream_t st) {
     const float sa = fabsf(a.scale), sgn = a.scale < 0.f ? -1.0f : 1.0f;
     if (a.ntiles > 0) {
         const dim3 grid((unsigned)a.ntiles, (unsigned)a.num_kv_heads), block(64 * G);
-        RPO_LAUNCH((causal_attn_bwd_dq_f32_kernel<HD, G>), grid, block, 0, st, a.q, a.k, a.v, a.out, a.dout, a.q_stride, a.k_stride,
-                   a.v_stride, a.out_stride, a.dout_stride, a.lse, a.cu_q, a.cu_k, a.tiles, (int)a.num_seqs, sa, sgn, a.scale, a.dq,
-                   a.dq_stride, a.ws);
+        RPO_LAUNCH((causal_attn_bwd_dq_f32_kernel<HD, G>), grid, block, 0, st, (const float*)a.q, (const float*)a.k, (const float*)a.v, (const float*)a.out, (const float*)a.dout, a.q_stride, a.k_stride,
+                   a.v_stride, a.out_stride, a.dout_stride, (const float*)a.lse, a.cu_q, a.cu_k, a.tiles, (int)a.num_seqs, sa, sgn, a.scale,
+                   (float*)a.dq, a.dq_stride, a.ws);
         if (hipPeekAtLastError() != hipSuccess) return;
     }
     if (a.nktiles > 0) {
         const dim3 grid((unsigned)a.nktiles, (unsigned)a.num_kv_heads), block(128);
-        RPO_LAUNCH((causal_attn_bwd_dkdv_f32_kernel<HD, G>), grid, block, 0, st, a.q, a.k, a.v, a.dout, a.q_stride, a.k_stride,
-                   a.v_stride, a.dout_stride, a.lse, (const float*)a.ws, a.cu_q, a.cu_k, a.k_tiles, (int)a.num_seqs, sa, sgn, a.scale,
-                   a.dk, a.dk_stride, a.dv, a.dv_stride);
+        RPO_LAUNCH((causal_attn_bwd_dkdv_f32_kernel<HD, G>), grid, block, 0, st, (const float*)a.q, (const float*)a.k, (const float*)a.v, (const float*)a.dout, a.q_stride, a.k_stride,
+                   a.v_stride, a.dout_stride, (const float*)a.lse, (const float*)a.ws, a.cu_q, a.cu_k, a.k_tiles, (int)a.num_seqs, sa, sgn,
+                   a.scale, (float*)a.dk, a.dk_stride, (float*)a.dv, a.dv_stride);
     }
 }
 
@@ -444,35 +422,16 @@ extern "C" int rpo_causal_attn_bwd_f32(const void* q, const void* k, const void*
                                        int64_t q_block, int64_t num_seqs, int64_t num_heads, int64_t num_kv_heads, int64_t head_dim,
                                        float scale, void* dq, int64_t dq_stride, void* dk, int64_t dk_stride, void* dv,
                                        int64_t dv_stride, float* ws, rpo_stream_t stream) {
-    if (!q || !k || !v || !out || !dout || !lse || !cu_seqlens_q || !cu_seqlens_k || !tiles || !k_tiles || !dq || !dk || !dv ||
-        !ws || ntiles < 0 || nktiles < 0 || num_seqs <= 0 || num_seqs >= 0x7fffffff || num_heads <= 0 || num_kv_heads <= 0 ||
-        head_dim <= 0 || q_stride <= 0 || k_stride <= 0 || v_stride <= 0 || out_stride <= 0 || dout_stride <= 0 || dq_stride <= 0 ||
-        dk_stride <= 0 || dv_stride <= 0 || !(fabsf(scale) <= 3.0e38f))
-        return RPO_ERR_INVALID_ARG;
-    if ((head_dim != 64 && head_dim != 128) || num_heads % num_kv_heads != 0 || tile_cols != 2 || q_block != kQBlock ||
-        ntiles > 0x7fffffff || nktiles > 0x7fffffff || num_kv_heads > 65535)
-        return RPO_ERR_UNSUPPORTED;
-    const int64_t group = num_heads / num_kv_heads;
-    if (group != 1 && group != 2 && group != 4 && group != 8) return RPO_ERR_UNSUPPORTED;
-    if (!rpo_aligned16(q) || !rpo_aligned16(k) || !rpo_aligned16(v) || !rpo_aligned16(out) || !rpo_aligned16(dout) ||
-        !rpo_aligned16(dq) || !rpo_aligned16(dk) || !rpo_aligned16(dv) || !rpo_aligned16(ws) || q_stride % 4 || k_stride % 4 ||
-        v_stride % 4 || out_stride % 4 || dout_stride % 4 || dq_stride % 4 || dk_stride % 4 || dv_stride % 4)
-        return RPO_ERR_UNSUPPORTED;
+    HostArgs a{};
+    a.q = q, a.k = k, a.v = v, a.q_stride = q_stride, a.k_stride = k_stride, a.v_stride = v_stride;
+    a.cu_q = cu_seqlens_q, a.cu_k = cu_seqlens_k, a.tiles = tiles, a.ntiles = ntiles, a.tile_cols = tile_cols, a.q_block = q_block;
+    a.num_seqs = num_seqs, a.num_heads = num_heads, a.num_kv_heads = num_kv_heads, a.head_dim = head_dim, a.scale = scale;
+    a.out = const_cast<void*>(out), a.out_stride = out_stride, a.lse = const_cast<float*>(lse);
+    a.dout = dout, a.dout_stride = dout_stride, a.k_tiles = k_tiles, a.nktiles = nktiles;
+    a.dq = dq, a.dk = dk, a.dv = dv, a.dq_stride = dq_stride, a.dk_stride = dk_stride, a.dv_stride = dv_stride, a.ws = ws;
+    // 16-byte vectors of 4 floats; ws: 8-byte (delta, 1 / L') pairs, 16-byte aligned
+    if (const int rc = check_backward(a, 4, 16)) return rc;
     if (ntiles == 0 && nktiles == 0) return RPO_OK;
-    const Args a{(const float*)q, (const float*)k, (const float*)v, (const float*)out, (const float*)dout, q_stride, k_stride,
-                 v_stride, out_stride, dout_stride, lse, cu_seqlens_q, cu_seqlens_k, tiles, k_tiles, ntiles, nktiles, num_seqs,
-                 num_kv_heads, scale, (float*)dq, (float*)dk, (float*)dv, dq_stride, dk_stride, dv_stride, ws};
-    hipStream_t st = (hipStream_t)stream;
-#define RPO_CAUSAL_F32_BWD_CASE(HD, G) \
-    if (head_dim == HD && group == G) launch<HD, G>(a, st);
-    RPO_CAUSAL_F32_BWD_CASE(64, 1)
-    RPO_CAUSAL_F32_BWD_CASE(64, 2)
-    RPO_CAUSAL_F32_BWD_CASE(64, 4)
-    RPO_CAUSAL_F32_BWD_CASE(64, 8)
-    RPO_CAUSAL_F32_BWD_CASE(128, 1)
-    RPO_CAUSAL_F32_BWD_CASE(128, 2)
-    RPO_CAUSAL_F32_BWD_CASE(128, 4)
-    RPO_CAUSAL_F32_BWD_CASE(128, 8)
-#undef RPO_CAUSAL_F32_BWD_CASE
+    RPO_CAUSAL_ATTN_DISPATCH(launch, a, (hipStream_t)stream)
     return rpo_launch_status();
 }

@@ -243,19 +243,43 @@ def _checkpoint_contexts():
     return contextlib.nullcontext(), _ops.recomputing()
 
 
+# (storage dtype, grad mode) -> (module switch, model attribute, ops tag) of the native causal attention that can be opted in
+_NATIVE_ATTENTION = {(torch.float32, False): ("LLAMA_F32_ATTENTION", "f32_attention", "f32"),
+                     (torch.float32, True): ("LLAMA_F32_ATTENTION_TRAIN", "f32_attention_train", "f32"),
+                     (torch.float16, False): ("LLAMA_FP16_NATIVE", "native_fp16", "f16"),
+                     (torch.float16, True): ("LLAMA_FP16_NATIVE_TRAIN", "native_fp16_train", "f16")}
+
+
+def _native_attention_lists(enc, dtype, lens, device) -> dict:
+    """The work lists of the native causal attention that `enc` (a LlamaEncoder) opted in to for packed tokens of `dtype` under the
+    current grad mode, as the VarlenCtx attributes that send the attention there; {} where nothing is opted in or the kernel
+    refuses the head shape.  Under no-grad the two query lists of `ops.causal_attn_<tag>`: `<tag>_tiles` for the full blocks
+    (lens, lens) and `<tag>_last_tiles` for the last block's one query per sequence ([1] * N, lens); under grad mode the key lists
+    of `ops.causal_attn_<tag>_train` beside them (`<tag>_k_tiles`, `<tag>_last_k_tiles`).  Built from the host lengths, uploaded
+    asynchronously."""
+    kind = _NATIVE_ATTENTION.get((dtype, torch.is_grad_enabled()))
+    if kind is None:
+        return {}
+    switch, attr, tag = kind
+    cfg = enc.config
+    if not ((globals()[switch] or getattr(enc, attr))
+            and getattr(_ops, f"causal_attn_{tag}_shape_ok")(cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim)):
+        return {}
+    forms = {"": lens, "_last": [1] * len(lens)}
+    lists = {f"{tag}{form}_tiles": getattr(_ops, f"causal_attn_{tag}_tile_table")(lq, lens, device) for form, lq in forms.items()}
+    if torch.is_grad_enabled():
+        lists.update({f"{tag}{form}_k_tiles": getattr(_ops, f"causal_attn_{tag}_key_tile_table")(lq, lens, device)
+                      for form, lq in forms.items()})
+    return lists
+
+
 class VarlenCtx:
     """cu_seqlens (int32, device), the host copy of the lengths and the longest length of a packed batch; the attention kernels'
     work lists: `tiles` (128 queries per entry: forward and dQ), `k_tiles` (dK/dV), `fwd_tiles` (the forward's own list where it has
-    one -- head_dim 128: 64 queries x 4 q heads per entry, `ops.attn_fwd_tile_table` -- else None); the work lists of
-    `ops.causal_attn_f32` where the f32 attention was opted in (else None): `f32_tiles` for the full blocks (lens, lens) and
-    `f32_last_tiles` for the last block's one query per sequence ([1] * N, lens); under grad mode with the f32 TRAINING attention
-    opted in, the same two query lists and the key lists of `ops.causal_attn_f32_train` beside them (`f32_k_tiles`,
-    `f32_last_k_tiles`; else None), which is what sends the attention there; the work lists of `ops.causal_attn_f16` where the
-    native fp16 pass was opted in (else None): `f16_tiles` (lens, lens) and `f16_last_tiles` ([1] * N, lens) -- attributes that
-    `pooled_last_token_multi` sets on the object (tests/test_llama_f32_train_host.py pins the constructor's parameter list);
-    under grad mode with the fp16 TRAINING attention opted in, the same two query lists and the key lists of
-    `ops.causal_attn_f16_train` beside them (`f16_k_tiles`, `f16_last_k_tiles`; else None), attributes as well, which is what
-    sends the attention there."""
+    one -- head_dim 128: 64 queries x 4 q heads per entry, `ops.attn_fwd_tile_table` -- else None); the lists of the native f32 /
+    fp16 causal attention where one was opted in (`_native_attention_lists`; else None), which `native_attention` reads.  The
+    f32 ones are also constructor arguments and the fp16 ones class attributes that `pooled_last_token_multi` sets on the object:
+    the host tests pin the constructor's parameter list."""
     f16_tiles = f16_last_tiles = None
     f16_k_tiles = f16_last_k_tiles = None
 
@@ -264,6 +288,24 @@ class VarlenCtx:
         self.cu, self.lens, self.max_len, self.tiles, self.k_tiles, self.fwd_tiles = cu, lens, max_len, tiles, k_tiles, fwd_tiles
         self.f32_tiles, self.f32_last_tiles = f32_tiles, f32_last_tiles
         self.f32_k_tiles, self.f32_last_k_tiles = f32_k_tiles, f32_last_k_tiles
+
+    def native_attention(self, q, k, v, last: bool = False):
+        """The native causal attention for q / k / v as `run(cu_q, scale) -> out [Tq, nh * hd]`, or None: fp16 or f32 storage whose
+        lists were built (full blocks, or with `last` the one-query-per-sequence form) and whose layout the kernel takes.  Under
+        no-grad one launch of the forward kernel for the batch; under grad mode the same kernel with lse and its backward as ONE
+        autograd node, which the key lists select."""
+        tag = {torch.float16: "f16", torch.float32: "f32"}.get(q.dtype)
+        if tag is None:
+            return None
+        form = "_last" if last else ""
+        tiles, k_tiles = getattr(self, f"{tag}{form}_tiles"), getattr(self, f"{tag}{form}_k_tiles")
+        if torch.is_grad_enabled():
+            if k_tiles is None or not getattr(_ops, f"causal_attn_{tag}_ok")(q, k, v):
+                return None
+            return lambda cu_q, scale: getattr(_ops, f"causal_attn_{tag}_train")(q, k, v, cu_q, self.cu, tiles, k_tiles, scale)
+        if tiles is None or not getattr(_ops, f"causal_attn_{tag}_ok")(q, k, v):
+            return None
+        return lambda cu_q, scale: getattr(_ops, f"causal_attn_{tag}")(q, k, v, cu_q, self.cu, tiles, scale)[0]
 
 
 def _ckpt_single_input(ctx) -> bool:
@@ -283,27 +325,14 @@ def _varlen_causal_attention(q, k, v, ctx: VarlenCtx):
                                       k_tiles=ctx.k_tiles,
                                       key_block=_ops.ATTN_KEY_BLOCK if q.shape[-1] == 64 else _ops.ATTN_KEY_BLOCK_HD128,
                                       fwd_tiles=ctx.fwd_tiles)
-    if (ctx.f16_tiles is not None and q.dtype == torch.float16 and not torch.is_grad_enabled()
-            and _ops.causal_attn_f16_ok(q, k, v)):
-        # fp16 storage, opted in (LLAMA_FP16_NATIVE / native_fp16), no-grad: one launch of the fp16-MFMA kernel for the batch
-        return _ops.causal_attn_f16(q, k, v, ctx.cu, ctx.cu, ctx.f16_tiles, 1.0 / math.sqrt(q.shape[-1]))[0].view(q.shape)
-    if (ctx.f16_k_tiles is not None and q.dtype == torch.float16 and torch.is_grad_enabled()
-            and _ops.causal_attn_f16_ok(q, k, v)):
-        # fp16 storage, opted in (LLAMA_FP16_NATIVE_TRAIN / native_fp16_train), grad mode: the same kernel with lse, and its
-        # backward as ONE autograd node
-        return _ops.causal_attn_f16_train(q, k, v, ctx.cu, ctx.cu, ctx.f16_tiles, ctx.f16_k_tiles,
-                                          1.0 / math.sqrt(q.shape[-1])).view(q.shape)
+    native = ctx.native_attention(q, k, v)
+    if native is not None:
+        # fp16 or f32 storage, opted in.  One branch in front of the flash op: that one takes 16-bit storage only, so the f32 kernel
+        # keeps its place behind it
+        return native(ctx.cu, 1.0 / math.sqrt(q.shape[-1])).view(q.shape)
     if q.is_cuda and q.dtype in (torch.bfloat16, torch.float16):
         return torch.ops.aten._flash_attention_forward(q, k, v, ctx.cu, ctx.cu, ctx.max_len, ctx.max_len, 0.0, True,
                                                        False)[0]
-    if ctx.f32_tiles is not None and not torch.is_grad_enabled() and _ops.causal_attn_f32_ok(q, k, v):
-        # f32 storage, opted in (LLAMA_F32_ATTENTION / f32_attention), no-grad: one launch of the f32-MFMA kernel for the batch
-        return _ops.causal_attn_f32(q, k, v, ctx.cu, ctx.cu, ctx.f32_tiles, 1.0 / math.sqrt(q.shape[-1]))[0].view(q.shape)
-    if ctx.f32_k_tiles is not None and torch.is_grad_enabled() and _ops.causal_attn_f32_ok(q, k, v):
-        # f32 storage, opted in (LLAMA_F32_ATTENTION_TRAIN / f32_attention_train), grad mode: the same kernel with lse, and its
-        # backward as ONE autograd node
-        return _ops.causal_attn_f32_train(q, k, v, ctx.cu, ctx.cu, ctx.f32_tiles, ctx.f32_k_tiles,
-                                          1.0 / math.sqrt(q.shape[-1])).view(q.shape)
     outs, o0 = [], 0                      # f32 or CPU (tests, config 1): one SDPA call per sequence
     for n in ctx.lens:
         a = F.scaled_dot_product_attention(q[o0:o0 + n].transpose(0, 1)[None], k[o0:o0 + n].transpose(0, 1)[None],
@@ -318,29 +347,14 @@ def _varlen_last_query_attention(q, k, v, ctx: VarlenCtx):
     """q [N, nh, hd]: ONE query per sequence (its last token); k/v [T, nkv, hd] packed.  The last token attends to
     every key of its own sequence, so no causal mask is needed."""
     N = q.shape[0]
-    if (ctx.f16_last_tiles is not None and q.dtype == torch.float16 and not torch.is_grad_enabled()
-            and _ops.causal_attn_f16_ok(q, k, v)):
-        # the same fp16 kernel with one query per sequence: bottom-right aligned, so that query sees every key
+    native = ctx.native_attention(q, k, v, last=True)
+    if native is not None:
+        # the same kernels with one query per sequence: bottom-right aligned, so that query sees every key
         cu_q = torch.arange(N + 1, device=q.device, dtype=torch.int32)
-        return _ops.causal_attn_f16(q, k, v, cu_q, ctx.cu, ctx.f16_last_tiles, 1.0 / math.sqrt(q.shape[-1]))[0].view(q.shape)
-    if (ctx.f16_last_k_tiles is not None and q.dtype == torch.float16 and torch.is_grad_enabled()
-            and _ops.causal_attn_f16_ok(q, k, v)):
-        # grad mode, opted in (LLAMA_FP16_NATIVE_TRAIN / native_fp16_train): the one-query form of the same autograd node
-        cu_q = torch.arange(N + 1, device=q.device, dtype=torch.int32)
-        return _ops.causal_attn_f16_train(q, k, v, cu_q, ctx.cu, ctx.f16_last_tiles, ctx.f16_last_k_tiles,
-                                          1.0 / math.sqrt(q.shape[-1])).view(q.shape)
+        return native(cu_q, 1.0 / math.sqrt(q.shape[-1])).view(q.shape)
     if q.is_cuda and q.dtype in (torch.bfloat16, torch.float16):
         cu_q = torch.arange(N + 1, device=q.device, dtype=torch.int32)
         return torch.ops.aten._flash_attention_forward(q, k, v, cu_q, ctx.cu, 1, ctx.max_len, 0.0, False, False)[0]
-    if ctx.f32_last_tiles is not None and not torch.is_grad_enabled() and _ops.causal_attn_f32_ok(q, k, v):
-        # the same kernel with one query per sequence: bottom-right aligned, so that query sees every key
-        cu_q = torch.arange(N + 1, device=q.device, dtype=torch.int32)
-        return _ops.causal_attn_f32(q, k, v, cu_q, ctx.cu, ctx.f32_last_tiles, 1.0 / math.sqrt(q.shape[-1]))[0].view(q.shape)
-    if ctx.f32_last_k_tiles is not None and torch.is_grad_enabled() and _ops.causal_attn_f32_ok(q, k, v):
-        # grad mode, opted in (LLAMA_F32_ATTENTION_TRAIN / f32_attention_train): the one-query form of the same autograd node
-        cu_q = torch.arange(N + 1, device=q.device, dtype=torch.int32)
-        return _ops.causal_attn_f32_train(q, k, v, cu_q, ctx.cu, ctx.f32_last_tiles, ctx.f32_last_k_tiles,
-                                          1.0 / math.sqrt(q.shape[-1])).view(q.shape)
     outs, o0 = [], 0
     for i, n in enumerate(ctx.lens):
         a = F.scaled_dot_product_attention(q[i:i + 1].transpose(0, 1)[None], k[o0:o0 + n].transpose(0, 1)[None],
@@ -774,45 +788,13 @@ class LlamaEncoder(nn.Module):
                 k_tiles = _ops.attn_key_tile_table(
                     lens, x.device, self.config.num_key_value_heads,
                     _ops.ATTN_KEY_BLOCK if self.config.head_dim == 64 else _ops.ATTN_KEY_BLOCK_HD128)
-        f32_tiles = f32_last_tiles = None
-        if ((LLAMA_F32_ATTENTION or self.f32_attention) and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled()
-                and _ops.causal_attn_f32_shape_ok(self.config.num_attention_heads, self.config.num_key_value_heads,
-                                                  self.config.head_dim)):
-            # opted in: the work lists of ops.causal_attn_f32 from the host lengths, uploaded asynchronously
-            f32_tiles = _ops.causal_attn_f32_tile_table(lens, lens, x.device)
-            f32_last_tiles = _ops.causal_attn_f32_tile_table([1] * N, lens, x.device)
-        f32_k_tiles = f32_last_k_tiles = None
-        if ((LLAMA_F32_ATTENTION_TRAIN or self.f32_attention_train) and x.is_cuda and x.dtype == torch.float32
-                and torch.is_grad_enabled()
-                and _ops.causal_attn_f32_shape_ok(self.config.num_attention_heads, self.config.num_key_value_heads,
-                                                  self.config.head_dim)):
-            # opted in, grad mode: the same two query lists and the key lists of ops.causal_attn_f32_train
-            f32_tiles = _ops.causal_attn_f32_tile_table(lens, lens, x.device)
-            f32_last_tiles = _ops.causal_attn_f32_tile_table([1] * N, lens, x.device)
-            f32_k_tiles = _ops.causal_attn_f32_key_tile_table(lens, lens, x.device)
-            f32_last_k_tiles = _ops.causal_attn_f32_key_tile_table([1] * N, lens, x.device)
-        f16_tiles = f16_last_tiles = None
-        if ((LLAMA_FP16_NATIVE or self.native_fp16) and x.is_cuda and x.dtype == torch.float16 and not torch.is_grad_enabled()
-                and _ops.causal_attn_f16_shape_ok(self.config.num_attention_heads, self.config.num_key_value_heads,
-                                                  self.config.head_dim)):
-            # opted in: the work lists of ops.causal_attn_f16 from the host lengths, uploaded asynchronously; the rest of the pass
-            # runs inside ops.fp16_native, which opens the fp16 row kernels
-            f16_tiles = _ops.causal_attn_f16_tile_table(lens, lens, x.device)
-            f16_last_tiles = _ops.causal_attn_f16_tile_table([1] * N, lens, x.device)
-        ctx = VarlenCtx(cu, lens, max(lens), tiles, k_tiles, fwd_tiles, f32_tiles, f32_last_tiles, f32_k_tiles=f32_k_tiles,
-                        f32_last_k_tiles=f32_last_k_tiles)
-        if ((LLAMA_FP16_NATIVE_TRAIN or self.native_fp16_train) and x.is_cuda and x.dtype == torch.float16
-                and torch.is_grad_enabled()
-                and _ops.causal_attn_f16_shape_ok(self.config.num_attention_heads, self.config.num_key_value_heads,
-                                                  self.config.head_dim)):
-            # opted in, grad mode: the two query lists and the key lists of ops.causal_attn_f16_train; attention only -- the pass
-            # does not enter ops.fp16_native (the row kernels have no fp16 backward)
-            ctx.f16_tiles = _ops.causal_attn_f16_tile_table(lens, lens, x.device)
-            ctx.f16_last_tiles = _ops.causal_attn_f16_tile_table([1] * N, lens, x.device)
-            ctx.f16_k_tiles = _ops.causal_attn_f16_key_tile_table(lens, lens, x.device)
-            ctx.f16_last_k_tiles = _ops.causal_attn_f16_key_tile_table([1] * N, lens, x.device)
-        if f16_tiles is not None:
-            ctx.f16_tiles, ctx.f16_last_tiles = f16_tiles, f16_last_tiles
+        ctx = VarlenCtx(cu, lens, max(lens), tiles, k_tiles, fwd_tiles)
+        native = _native_attention_lists(self, x.dtype, lens, x.device) if x.is_cuda else {}
+        for name, table in native.items():
+            setattr(ctx, name, table)
+        if "f16_tiles" in native and not torch.is_grad_enabled():
+            # the no-grad fp16 kind: the rest of the pass runs inside ops.fp16_native, which opens the fp16 row kernels (under grad
+            # mode attention only: the row kernels have no fp16 backward)
             with _ops.fp16_native():
                 return self._pooled_rows(batches, x, rope, ctx, cu, n_fill)
         return self._pooled_rows(batches, x, rope, ctx, cu, n_fill)

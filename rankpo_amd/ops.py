@@ -6,6 +6,7 @@ done by librankpo_hip.so.  There is no fallback: tensors must live on a HIP devi
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import threading
 from dataclasses import dataclass
 from typing import NamedTuple
@@ -1254,41 +1255,85 @@ def bidir_attn_fwd(q, k, v, cu_q, cu_k, tiles, scale, want_lse: bool = False):
 
 
 # ------------------------------------------------------------------------------------------------
-# (9c) causal f32 attention of the packed Llama pass (LlamaEncoder.pooled_last_token_multi under no-grad, opt-in; no autograd:
-# forward only).  Header section (9c), rankpo_amd/csrc/causal_attn_f32.hip.
+# (9c)-(9f) causal grouped-query attention of the packed Llama pass on f32 and on fp16 storage (opt-in: encoder.LLAMA_F32_ATTENTION
+# / _TRAIN, encoder.LLAMA_FP16_NATIVE / _TRAIN): forward, backward and the autograd Function over the pair.  Header sections
+# (9c)-(9f), rankpo_amd/csrc/causal_attn_{f32,f32_bwd,f16,f16_bwd}.hip.  ONE implementation, driven by a per-dtype record; the
+# public names of both dtypes are bindings of it.
 # ------------------------------------------------------------------------------------------------
-CAUSAL_ATTN_F32_Q_BLOCK = 32             # query rows per work-list entry (the only format the kernel takes)
+CAUSAL_ATTN_F32_Q_BLOCK = 32             # query (and key) rows per work-list entry (the only format the kernels take)
 CAUSAL_ATTN_F32_HEAD_DIMS = (64, 128)
 CAUSAL_ATTN_F32_GROUPS = (1, 2, 4, 8)    # query heads per kv head
+CAUSAL_ATTN_F16_Q_BLOCK = CAUSAL_ATTN_F32_Q_BLOCK    # one list format, one set of shapes
+CAUSAL_ATTN_F16_HEAD_DIMS = CAUSAL_ATTN_F32_HEAD_DIMS
+CAUSAL_ATTN_F16_GROUPS = CAUSAL_ATTN_F32_GROUPS
 
 
-def causal_attn_f32_tile_list(lens_q, lens_k):
-    """The work list of `causal_attn_f32` as a host numpy int32 [n, 2] = (sequence id, first query row): one entry per (sequence,
-    block of 32 queries).  Query i of a sequence sees the keys j <= i + (lk - lq), and an entry runs until the last visible key of
-    its last query: the entries whose last visible key lies furthest, the longest-running ones, come first.  lens_q[n] > lens_k[n]
-    (a query in front of every key) raises ValueError."""
+class _CausalAttnKind(NamedTuple):
+    """What differs between the f32 and the fp16 instantiation on the host."""
+    tag: str             # f32 / f16: the entries are rpo_causal_attn_{fwd,bwd}_<tag>, the raw ops <name> and <name>_bwd
+    dtype: torch.dtype
+    stride_mult: int     # elements per 16 bytes: token strides are multiples of it
+    ws_tail: tuple       # the backward's workspace is f32 [nh, Tq, *ws_tail]: (delta, 1 / L') pairs for f32, delta for fp16
+    fused_grads: bool    # dq / dk / dv as column blocks of ONE [T, (nh + 2 nkv) hd] buffer (dq + fused dk|dv where Tq != Tk), as
+    #                      the q|k|v projection output lies; False: three contiguous tensors
+
+    @property
+    def name(self):
+        return "causal_attn_" + self.tag
+
+
+_CAUSAL_F32 = _CausalAttnKind("f32", torch.float32, 4, (2,), False)
+_CAUSAL_F16 = _CausalAttnKind("f16", torch.float16, 8, (), True)
+
+
+def _causal_attn_block_list(name, lens_q, lens_k, of_keys: bool):
+    """Host numpy int32 [n, 2] = (sequence id, first row): one entry per (sequence, block of 32 queries), or of 32 keys with
+    `of_keys` (sequences without queries included: their dk / dv rows are zero-filled).  Query i of a sequence sees the keys
+    j <= i + (lk - lq).  The longest-running entries come first: a query entry runs until the last visible key of its last query,
+    a key entry walks the queries that see its first key, lq - max(0, k0 - (lk - lq)) of them."""
     import numpy as np
-    qb = CAUSAL_ATTN_F32_Q_BLOCK
+    blk = CAUSAL_ATTN_F32_Q_BLOCK
     lq = np.asarray(lens_q, dtype=np.int64).reshape(-1)
     lk = np.asarray(lens_k, dtype=np.int64).reshape(-1)
     if lq.shape != lk.shape:
-        raise ValueError("causal_attn_f32_tile_list: one query length and one key length per sequence")
+        raise ValueError(f"{name}: one query length and one key length per sequence")
     if (lq > lk).any() or (lq < 0).any():
-        raise ValueError("causal_attn_f32_tile_list: 0 <= lens_q[n] <= lens_k[n] is required (bottom-right aligned causal mask)")
-    nt = (lq + qb - 1) // qb
+        raise ValueError(f"{name}: 0 <= lens_q[n] <= lens_k[n] is required (bottom-right aligned causal mask)")
+    nt = ((lk if of_keys else lq) + blk - 1) // blk
     seq = np.repeat(np.arange(len(lq)), nt)
-    q0 = (np.arange(int(nt.sum())) - np.repeat(np.cumsum(nt) - nt, nt)) * qb
-    last_key = np.minimum(q0 + qb, lq[seq]) - 1 + (lk - lq)[seq]
-    order = np.argsort(-last_key, kind="stable")
-    return np.stack([seq[order], q0[order]], 1).astype(np.int32).reshape(-1, 2)
+    r0 = (np.arange(int(nt.sum())) - np.repeat(np.cumsum(nt) - nt, nt)) * blk
+    shift = (lk - lq)[seq]
+    work = lq[seq] - np.maximum(0, r0 - shift) if of_keys else np.minimum(r0 + blk, lq[seq]) - 1 + shift
+    order = np.argsort(-work, kind="stable")
+    return np.stack([seq[order], r0[order]], 1).astype(np.int32).reshape(-1, 2)
 
 
-def causal_attn_f32_tile_table(lens_q, lens_k, device):
-    """`causal_attn_f32_tile_list` on the device: a pinned, asynchronous upload (nothing waits for it on the host)."""
-    t = torch.from_numpy(causal_attn_f32_tile_list(lens_q, lens_k))
+def _tile_upload(table, device):
+    """A host work list on the device: a pinned, asynchronous upload (nothing waits for it on the host)."""
+    t = torch.from_numpy(table)
     if torch.device(device).type == "cuda":
         t = t.pin_memory()
     return t.to(device, non_blocking=True)
+
+
+def causal_attn_f32_tile_list(lens_q, lens_k):
+    """The work list of `causal_attn_f32` / `_f16`: `_causal_attn_block_list` over the queries.  lens_q[n] > lens_k[n] (a query in
+    front of every key) raises ValueError."""
+    return _causal_attn_block_list("causal_attn_f32_tile_list", lens_q, lens_k, False)
+
+
+def causal_attn_f32_key_tile_list(lens_q, lens_k):
+    """The key work list of `causal_attn_f32_bwd` / `_f16_bwd`: `_causal_attn_block_list` over the keys.  Raises ValueError in the
+    cases `causal_attn_f32_tile_list` does."""
+    return _causal_attn_block_list("causal_attn_f32_key_tile_list", lens_q, lens_k, True)
+
+
+def causal_attn_f32_tile_table(lens_q, lens_k, device):
+    return _tile_upload(causal_attn_f32_tile_list(lens_q, lens_k), device)
+
+
+def causal_attn_f32_key_tile_table(lens_q, lens_k, device):
+    return _tile_upload(causal_attn_f32_key_tile_list(lens_q, lens_k), device)
 
 
 def causal_attn_f32_shape_ok(num_heads: int, num_kv_heads: int, head_dim: int) -> bool:
@@ -1296,261 +1341,124 @@ def causal_attn_f32_shape_ok(num_heads: int, num_kv_heads: int, head_dim: int) -
             and num_heads // num_kv_heads in CAUSAL_ATTN_F32_GROUPS)
 
 
-def causal_attn_f32_ok(q, k, v) -> bool:
-    """What rpo_causal_attn_fwd_f32 takes, restated: float32 on a HIP device, q [Tq, nh, hd] and k / v [Tk, nkv, hd] with heads
-    contiguous inside a token row, head_dim 64 or 128, nh / nkv in (1, 2, 4, 8), 16-byte aligned with token strides % 4 == 0."""
-    if not all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 for t in (q, k, v)):
+def _causal_attn_ok(kind, q, k, v) -> bool:
+    """What the entries of `kind` take, restated: its dtype on a HIP device, q [Tq, nh, hd] and k / v [Tk, nkv, hd] with heads
+    contiguous inside a token row, head_dim 64 or 128, nh / nkv in (1, 2, 4, 8), 16-byte aligned with token strides a multiple of
+    16 bytes."""
+    if not all(t.is_cuda and t.dtype == kind.dtype and t.dim() == 3 for t in (q, k, v)):
         return False
     hd = q.shape[2]
     if k.shape != v.shape or k.shape[2] != hd or not causal_attn_f32_shape_ok(q.shape[1], k.shape[1], hd):
         return False
-    return all(t.stride(2) == 1 and t.stride(1) == hd and t.stride(0) % 4 == 0 and t.stride(0) > 0 and t.data_ptr() % 16 == 0
-               for t in (q, k, v))
+    return all(t.stride(2) == 1 and t.stride(1) == hd and t.stride(0) % kind.stride_mult == 0 and t.stride(0) > 0
+               and t.data_ptr() % 16 == 0 for t in (q, k, v))
 
 
-def causal_attn_f32(q, k, v, cu_q, cu_k, tiles, scale, want_lse: bool = False):
-    """Causal grouped-query variable-length attention on f32 storage: q [Tq, nh, hd], k / v [Tk, nkv, hd] (heads contiguous, token
-    stride free: column blocks of one fused projection output), cu_q / cu_k int32 [N + 1] on the device, tiles from
+def _causal_attn_check(kind, fn, q, k, v, cu_q, cu_k, *lists):
+    if not _causal_attn_ok(kind, q, k, v):
+        raise ValueError(f"{fn}: {str(kind.dtype)[6:]} HIP tensors [T, heads, head_dim] with head_dim in (64, 128), 1 / 2 / 4 / 8 "
+                         f"query heads per kv head, heads contiguous, 16-byte aligned, token strides % {kind.stride_mult} == 0")
+    if (cu_q.numel() != cu_k.numel() or cu_q.dtype != torch.int32 or cu_k.dtype != torch.int32
+            or not all(t.dtype == torch.int32 and t.dim() == 2 and t.shape[1] == 2 and t.is_contiguous() for t in lists)):
+        raise ValueError(f"{fn}: cu_q / cu_k int32 [N + 1], {' / '.join(['tiles', 'k_tiles'][:len(lists)])} int32 [n, 2]")
+
+
+def _causal_attn_fwd(kind, q, k, v, cu_q, cu_k, tiles, scale, want_lse: bool = False):
+    """Causal grouped-query variable-length attention: q [Tq, nh, hd], k / v [Tk, nkv, hd] (heads contiguous, token stride free:
+    column blocks of one fused projection output), cu_q / cu_k int32 [N + 1] on the device, tiles from
     `causal_attn_f32_tile_table(lens_q, lens_k)` (which checks lens_q <= lens_k).  Query i of sequence n sees its keys
-    j <= i + (lk - lq).  Returns (out [Tq, nh * hd], lse f32 [nh, Tq] or None).  Forward only: no autograd node."""
-    if not causal_attn_f32_ok(q, k, v):
-        raise ValueError("causal_attn_f32: float32 HIP tensors [T, heads, head_dim] with head_dim in (64, 128), 1 / 2 / 4 / 8 query "
-                         "heads per kv head, heads contiguous, 16-byte aligned, token strides % 4 == 0")
-    if cu_q.numel() != cu_k.numel() or cu_q.dtype != torch.int32 or cu_k.dtype != torch.int32 or tiles.dtype != torch.int32:
-        raise ValueError("causal_attn_f32: cu_q / cu_k int32 [N + 1], tiles int32 [n, 2]")
-    lib = _lib.load()
+    j <= i + (lk - lq).  Returns (out [Tq, nh * hd] of q's dtype, lse f32 [nh, Tq] or None).  Forward only: no autograd node."""
+    _causal_attn_check(kind, kind.name, q, k, v, cu_q, cu_k, tiles)
+    entry = "rpo_causal_attn_fwd_" + kind.tag
     Tq, nh, hd = q.shape
     out = torch.empty((Tq, nh * hd), dtype=q.dtype, device=q.device)
     lse = torch.empty((nh, Tq), dtype=torch.float32, device=q.device) if want_lse else None
     with torch.cuda.device(q.device):
-        check(lib.rpo_causal_attn_fwd_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(0), k.stride(0), v.stride(0),
+        check(getattr(_lib.load(), entry)(q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(0), k.stride(0), v.stride(0),
                                           cu_q.data_ptr(), cu_k.data_ptr(), tiles.data_ptr(), tiles.shape[0], tiles.shape[1],
                                           CAUSAL_ATTN_F32_Q_BLOCK, cu_q.numel() - 1, nh, k.shape[1], hd, float(scale),
-                                          out.data_ptr(), nh * hd, _p(lse), _stream(q)), "rpo_causal_attn_fwd_f32")
+                                          out.data_ptr(), nh * hd, _p(lse), _stream(q)), entry)
     return out, lse
 
 
-# ------------------------------------------------------------------------------------------------
-# (9e) causal fp16 attention of the packed Llama pass (LlamaEncoder.pooled_last_token_multi under no-grad, opt-in:
-# encoder.LLAMA_FP16_NATIVE; no autograd: forward only).  Header section (9e), rankpo_amd/csrc/causal_attn_f16.hip.
-# ------------------------------------------------------------------------------------------------
-CAUSAL_ATTN_F16_Q_BLOCK = CAUSAL_ATTN_F32_Q_BLOCK    # the kernel takes the 32-query entries of (9c): one list format
-CAUSAL_ATTN_F16_HEAD_DIMS = (64, 128)
-CAUSAL_ATTN_F16_GROUPS = (1, 2, 4, 8)
-causal_attn_f16_tile_list = causal_attn_f32_tile_list
-causal_attn_f16_tile_table = causal_attn_f32_tile_table
-
-
-def causal_attn_f16_shape_ok(num_heads: int, num_kv_heads: int, head_dim: int) -> bool:
-    return (head_dim in CAUSAL_ATTN_F16_HEAD_DIMS and num_kv_heads > 0 and num_heads % num_kv_heads == 0
-            and num_heads // num_kv_heads in CAUSAL_ATTN_F16_GROUPS)
-
-
-def causal_attn_f16_ok(q, k, v) -> bool:
-    """What rpo_causal_attn_fwd_f16 takes, restated: float16 on a HIP device, q [Tq, nh, hd] and k / v [Tk, nkv, hd] with heads
-    contiguous inside a token row, head_dim 64 or 128, nh / nkv in (1, 2, 4, 8), 16-byte aligned with token strides % 8 == 0."""
-    if not all(t.is_cuda and t.dtype == torch.float16 and t.dim() == 3 for t in (q, k, v)):
-        return False
-    hd = q.shape[2]
-    if k.shape != v.shape or k.shape[2] != hd or not causal_attn_f16_shape_ok(q.shape[1], k.shape[1], hd):
-        return False
-    return all(t.stride(2) == 1 and t.stride(1) == hd and t.stride(0) % 8 == 0 and t.stride(0) > 0 and t.data_ptr() % 16 == 0
-               for t in (q, k, v))
-
-
-def causal_attn_f16(q, k, v, cu_q, cu_k, tiles, scale, want_lse: bool = False):
-    """Causal grouped-query variable-length attention on fp16 storage: q [Tq, nh, hd], k / v [Tk, nkv, hd] (heads contiguous, token
-    stride free: column blocks of one fused projection output), cu_q / cu_k int32 [N + 1] on the device, tiles from
-    `causal_attn_f16_tile_table(lens_q, lens_k)` (which checks lens_q <= lens_k).  Query i of sequence n sees its keys
-    j <= i + (lk - lq).  Returns (out fp16 [Tq, nh * hd], lse f32 [nh, Tq] or None).  Forward only: no autograd node."""
-    if not causal_attn_f16_ok(q, k, v):
-        raise ValueError("causal_attn_f16: float16 HIP tensors [T, heads, head_dim] with head_dim in (64, 128), 1 / 2 / 4 / 8 query "
-                         "heads per kv head, heads contiguous, 16-byte aligned, token strides % 8 == 0")
-    if (cu_q.numel() != cu_k.numel() or cu_q.dtype != torch.int32 or cu_k.dtype != torch.int32 or tiles.dtype != torch.int32
-            or tiles.dim() != 2 or tiles.shape[1] != 2 or not tiles.is_contiguous()):
-        raise ValueError("causal_attn_f16: cu_q / cu_k int32 [N + 1], tiles int32 [n, 2]")
-    lib = _lib.load()
-    Tq, nh, hd = q.shape
-    out = torch.empty((Tq, nh * hd), dtype=q.dtype, device=q.device)
-    lse = torch.empty((nh, Tq), dtype=torch.float32, device=q.device) if want_lse else None
-    with torch.cuda.device(q.device):
-        check(lib.rpo_causal_attn_fwd_f16(q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(0), k.stride(0), v.stride(0),
-                                          cu_q.data_ptr(), cu_k.data_ptr(), tiles.data_ptr(), tiles.shape[0], tiles.shape[1],
-                                          CAUSAL_ATTN_F16_Q_BLOCK, cu_q.numel() - 1, nh, k.shape[1], hd, float(scale),
-                                          out.data_ptr(), nh * hd, _p(lse), _stream(q)), "rpo_causal_attn_fwd_f16")
-    return out, lse
-
-
-# ------------------------------------------------------------------------------------------------
-# (9d) the backward of (9c) and the autograd Function over the pair: the attention of the packed f32 Llama TRAINING pass
-# (opt-in: encoder.LLAMA_F32_ATTENTION_TRAIN).  Header section (9d), rankpo_amd/csrc/causal_attn_f32_bwd.hip.
-# ------------------------------------------------------------------------------------------------
-def causal_attn_f32_key_tile_list(lens_q, lens_k):
-    """The key work list of `causal_attn_f32_bwd` as a host numpy int32 [n, 2] = (sequence id, first key row): one entry per
-    (sequence with keys, block of 32 keys), sequences without queries included (their dk / dv rows are zero-filled).  An entry
-    walks the queries that see its first key, lq - max(0, k0 - (lk - lq)) of them: the entries with the most come first.
-    Raises ValueError in the cases `causal_attn_f32_tile_list` does."""
-    import numpy as np
-    kb = CAUSAL_ATTN_F32_Q_BLOCK
-    lq = np.asarray(lens_q, dtype=np.int64).reshape(-1)
-    lk = np.asarray(lens_k, dtype=np.int64).reshape(-1)
-    if lq.shape != lk.shape:
-        raise ValueError("causal_attn_f32_key_tile_list: one query length and one key length per sequence")
-    if (lq > lk).any() or (lq < 0).any():
-        raise ValueError("causal_attn_f32_key_tile_list: 0 <= lens_q[n] <= lens_k[n] is required (bottom-right aligned causal mask)")
-    nt = (lk + kb - 1) // kb
-    seq = np.repeat(np.arange(len(lk)), nt)
-    k0 = (np.arange(int(nt.sum())) - np.repeat(np.cumsum(nt) - nt, nt)) * kb
-    visible = lq[seq] - np.maximum(0, k0 - (lk - lq)[seq])
-    order = np.argsort(-visible, kind="stable")
-    return np.stack([seq[order], k0[order]], 1).astype(np.int32).reshape(-1, 2)
-
-
-def causal_attn_f32_key_tile_table(lens_q, lens_k, device):
-    """`causal_attn_f32_key_tile_list` on the device: a pinned, asynchronous upload (nothing waits for it on the host)."""
-    t = torch.from_numpy(causal_attn_f32_key_tile_list(lens_q, lens_k))
-    if torch.device(device).type == "cuda":
-        t = t.pin_memory()
-    return t.to(device, non_blocking=True)
-
-
-def causal_attn_f32_bwd(q, k, v, out, lse, dout, cu_q, cu_k, tiles, k_tiles, scale):
-    """The gradients of `causal_attn_f32`: (dq [Tq, nh, hd], dk [Tk, nkv, hd], dv [Tk, nkv, hd]), float32, from its inputs, its
-    results (out [Tq, nh * hd], lse [nh, Tq]) and dout (the shape of out or of q).  tiles as the forward's, k_tiles from
-    `causal_attn_f32_key_tile_table` on the same lengths.  One entry, two launches (dQ, then dK/dV), no atomics: deterministic,
-    and independent of what else is packed in the batch.  The raw op: no autograd node."""
-    if not causal_attn_f32_ok(q, k, v):
-        raise ValueError("causal_attn_f32_bwd: float32 HIP tensors [T, heads, head_dim] with head_dim in (64, 128), 1 / 2 / 4 / 8 "
-                         "query heads per kv head, heads contiguous, 16-byte aligned, token strides % 4 == 0")
-    if (cu_q.numel() != cu_k.numel() or cu_q.dtype != torch.int32 or cu_k.dtype != torch.int32 or tiles.dtype != torch.int32
-            or k_tiles.dtype != torch.int32 or tiles.dim() != 2 or k_tiles.dim() != 2 or tiles.shape[1] != k_tiles.shape[1]):
-        raise ValueError("causal_attn_f32_bwd: cu_q / cu_k int32 [N + 1], tiles / k_tiles int32 [n, 2]")
+def _causal_attn_bwd(kind, q, k, v, out, lse, dout, cu_q, cu_k, tiles, k_tiles, scale):
+    """The gradients of the forward: (dq [Tq, nh, hd], dk [Tk, nkv, hd], dv [Tk, nkv, hd]) of q's dtype (fp16: column blocks of
+    ONE fused buffer, see `_CausalAttnKind.fused_grads`), from its inputs, its results (out [Tq, nh * hd], lse f32 [nh, Tq]) and
+    dout (the shape of out or of q).  tiles as the forward's, k_tiles from `causal_attn_f32_key_tile_table` on the same lengths.
+    One entry, two launches (dQ, then dK/dV), no atomics: deterministic, and independent of what else is packed in the batch.
+    The raw op: no autograd node."""
+    fn = kind.name + "_bwd"
+    _causal_attn_check(kind, fn, q, k, v, cu_q, cu_k, tiles, k_tiles)
     Tq, nh, hd = q.shape
     Tk, nkv, _ = k.shape
-    if (out.dtype != torch.float32 or dout.dtype != torch.float32 or lse.dtype != torch.float32 or out.numel() != q.numel()
+    if (out.dtype != kind.dtype or dout.dtype != kind.dtype or lse.dtype != torch.float32 or out.numel() != q.numel()
             or dout.numel() != q.numel() or lse.shape != (nh, Tq) or not lse.is_contiguous()):
-        raise ValueError("causal_attn_f32_bwd: out / dout float32 [Tq, nh * hd], lse float32 [nh, Tq] contiguous")
+        raise ValueError(f"{fn}: out / dout {str(kind.dtype)[6:]} [Tq, nh * hd], lse float32 [nh, Tq] contiguous")
 
-    def rows(t):       # [Tq, nh * hd] with contiguous rows, 16-byte aligned, token stride % 4 == 0: as it is, else a copy
+    def rows(t):       # [Tq, nh * hd] with contiguous rows, 16-byte aligned, token stride a multiple of 16 bytes: as it is, else a copy
         t = t.reshape(Tq, nh * hd)                      # a view wherever the strides allow one
-        if t.stride(1) != 1 or t.stride(0) % 4 or t.stride(0) <= 0 or t.data_ptr() % 16:
+        if t.stride(1) != 1 or t.stride(0) % kind.stride_mult or t.stride(0) <= 0 or t.data_ptr() % 16:
             t = t.contiguous()
         return t
     out, dout = rows(out), rows(dout)
-    lib = _lib.load()
-    dq = torch.empty((Tq, nh, hd), dtype=torch.float32, device=q.device)
-    dk = torch.empty((Tk, nkv, hd), dtype=torch.float32, device=q.device)
-    dv = torch.empty((Tk, nkv, hd), dtype=torch.float32, device=q.device)
-    ws = torch.empty((nh, Tq, 2), dtype=torch.float32, device=q.device)
+    new = lambda *shape: torch.empty(shape, dtype=kind.dtype, device=q.device)
+    if not kind.fused_grads:
+        dq, dk, dv = new(Tq, nh, hd), new(Tk, nkv, hd), new(Tk, nkv, hd)
+    elif Tq == Tk:     # self-attention: one fused gradient buffer, as the q|k|v projection output lies
+        dq, dk, dv = (t.view(Tq, -1, hd) for t in new(Tq, (nh + 2 * nkv) * hd).split([nh * hd, nkv * hd, nkv * hd], 1))
+    else:
+        dq = new(Tq, nh, hd)
+        dk, dv = (t.view(Tk, nkv, hd) for t in new(Tk, 2 * nkv * hd).split(nkv * hd, 1))
+    ws = torch.empty((nh, Tq) + kind.ws_tail, dtype=torch.float32, device=q.device)
+    entry = "rpo_causal_attn_bwd_" + kind.tag
     with torch.cuda.device(q.device):
-        check(lib.rpo_causal_attn_bwd_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(), q.stride(0),
+        check(getattr(_lib.load(), entry)(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(), q.stride(0),
                                           k.stride(0), v.stride(0), out.stride(0), dout.stride(0), lse.data_ptr(), cu_q.data_ptr(),
                                           cu_k.data_ptr(), tiles.data_ptr(), tiles.shape[0], k_tiles.data_ptr(), k_tiles.shape[0],
                                           tiles.shape[1], CAUSAL_ATTN_F32_Q_BLOCK, cu_q.numel() - 1, nh, nkv, hd, float(scale),
-                                          dq.data_ptr(), nh * hd, dk.data_ptr(), nkv * hd, dv.data_ptr(), nkv * hd, ws.data_ptr(),
-                                          _stream(q)), "rpo_causal_attn_bwd_f32")
-    return dq, dk, dv
-
-
-class _CausalAttnF32Train(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, q, k, v, cu_q, cu_k, tiles, k_tiles, scale):
-        out, lse = causal_attn_f32(q, k, v, cu_q, cu_k, tiles, scale, want_lse=True)
-        ctx.save_for_backward(q, k, v, out, lse, cu_q, cu_k, tiles, k_tiles)
-        ctx.scale = scale
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        q, k, v, out, lse, cu_q, cu_k, tiles, k_tiles = ctx.saved_tensors
-        dq, dk, dv = causal_attn_f32_bwd(q, k, v, out, lse, dout, cu_q, cu_k, tiles, k_tiles, ctx.scale)
-        return dq, dk, dv, None, None, None, None, None
-
-
-def causal_attn_f32_train(q, k, v, cu_q, cu_k, tiles, k_tiles, scale):
-    """`causal_attn_f32` with a gradient: an autograd Function over (q, k, v), column-block views of the fused projection output
-    included.  Forward: `causal_attn_f32(..., want_lse=True)` (the same deterministic kernel, also when a checkpointed block
-    recomputes it); saved: q, k, v, out, lse; backward: ONE call of `causal_attn_f32_bwd` (dout of any stride: made contiguous
-    only if needed).  Returns out [Tq, nh * hd]."""
-    return _CausalAttnF32Train.apply(q, k, v, cu_q, cu_k, tiles, k_tiles, scale)
-
-
-# ------------------------------------------------------------------------------------------------
-# (9f) the backward of (9e) and the autograd Function over the pair: the attention of the packed fp16 Llama TRAINING pass
-# (opt-in: encoder.LLAMA_FP16_NATIVE_TRAIN).  Header section (9f), rankpo_amd/csrc/causal_attn_f16_bwd.hip.
-# ------------------------------------------------------------------------------------------------
-causal_attn_f16_key_tile_list = causal_attn_f32_key_tile_list      # the 32-key entries of (9d): one list format
-causal_attn_f16_key_tile_table = causal_attn_f32_key_tile_table
-
-
-def causal_attn_f16_bwd(q, k, v, out, lse, dout, cu_q, cu_k, tiles, k_tiles, scale):
-    """The gradients of `causal_attn_f16`: (dq [Tq, nh, hd], dk [Tk, nkv, hd], dv [Tk, nkv, hd]), float16, column blocks of ONE
-    fused [T, (nh + 2 nkv) hd] buffer where Tq == Tk, from its inputs, its results (out fp16 [Tq, nh * hd], lse f32 [nh, Tq]) and
-    dout (the shape of out or of q).  tiles as the forward's, k_tiles from `causal_attn_f16_key_tile_table` on the same lengths.
-    One entry, two launches (dQ, then dK/dV), no atomics: deterministic, and independent of what else is packed in the batch.
-    The raw op: no autograd node."""
-    if not causal_attn_f16_ok(q, k, v):
-        raise ValueError("causal_attn_f16_bwd: float16 HIP tensors [T, heads, head_dim] with head_dim in (64, 128), 1 / 2 / 4 / 8 "
-                         "query heads per kv head, heads contiguous, 16-byte aligned, token strides % 8 == 0")
-    if (cu_q.numel() != cu_k.numel() or cu_q.dtype != torch.int32 or cu_k.dtype != torch.int32 or tiles.dtype != torch.int32
-            or k_tiles.dtype != torch.int32 or tiles.dim() != 2 or k_tiles.dim() != 2 or tiles.shape[1] != 2
-            or k_tiles.shape[1] != 2 or not tiles.is_contiguous() or not k_tiles.is_contiguous()):
-        raise ValueError("causal_attn_f16_bwd: cu_q / cu_k int32 [N + 1], tiles / k_tiles int32 [n, 2]")
-    Tq, nh, hd = q.shape
-    Tk, nkv, _ = k.shape
-    if (out.dtype != torch.float16 or dout.dtype != torch.float16 or lse.dtype != torch.float32 or out.numel() != q.numel()
-            or dout.numel() != q.numel() or lse.shape != (nh, Tq) or not lse.is_contiguous()):
-        raise ValueError("causal_attn_f16_bwd: out / dout float16 [Tq, nh * hd], lse float32 [nh, Tq] contiguous")
-
-    def rows(t):       # [Tq, nh * hd] with contiguous rows, 16-byte aligned, token stride % 8 == 0: as it is, else a copy
-        t = t.reshape(Tq, nh * hd)                      # a view wherever the strides allow one
-        if t.stride(1) != 1 or t.stride(0) % 8 or t.stride(0) <= 0 or t.data_ptr() % 16:
-            t = t.contiguous()
-        return t
-    out, dout = rows(out), rows(dout)
-    lib = _lib.load()
-    if Tq == Tk:       # self-attention: one fused gradient buffer, as the q|k|v projection output lies
-        fused = torch.empty((Tq, (nh + 2 * nkv) * hd), dtype=torch.float16, device=q.device)
-        dq = fused[:, :nh * hd].view(Tq, nh, hd)
-        dk = fused[:, nh * hd:(nh + nkv) * hd].view(Tk, nkv, hd)
-        dv = fused[:, (nh + nkv) * hd:].view(Tk, nkv, hd)
-    else:
-        dq = torch.empty((Tq, nh, hd), dtype=torch.float16, device=q.device)
-        fused = torch.empty((Tk, 2 * nkv * hd), dtype=torch.float16, device=q.device)
-        dk = fused[:, :nkv * hd].view(Tk, nkv, hd)
-        dv = fused[:, nkv * hd:].view(Tk, nkv, hd)
-    ws = torch.empty((nh, Tq), dtype=torch.float32, device=q.device)
-    with torch.cuda.device(q.device):
-        check(lib.rpo_causal_attn_bwd_f16(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(), q.stride(0),
-                                          k.stride(0), v.stride(0), out.stride(0), dout.stride(0), lse.data_ptr(), cu_q.data_ptr(),
-                                          cu_k.data_ptr(), tiles.data_ptr(), tiles.shape[0], k_tiles.data_ptr(), k_tiles.shape[0],
-                                          tiles.shape[1], CAUSAL_ATTN_F16_Q_BLOCK, cu_q.numel() - 1, nh, nkv, hd, float(scale),
                                           dq.data_ptr(), dq.stride(0), dk.data_ptr(), dk.stride(0), dv.data_ptr(), dv.stride(0),
-                                          ws.data_ptr(), _stream(q)), "rpo_causal_attn_bwd_f16")
+                                          ws.data_ptr(), _stream(q)), entry)
     return dq, dk, dv
 
 
-class _CausalAttnF16Train(torch.autograd.Function):
+class _CausalAttnTrain(torch.autograd.Function):
+    """The forward with lse and ONE backward call, through the module's public names of `kind` (what a test or tool wraps)."""
+
     @staticmethod
-    def forward(ctx, q, k, v, cu_q, cu_k, tiles, k_tiles, scale):
-        out, lse = causal_attn_f16(q, k, v, cu_q, cu_k, tiles, scale, want_lse=True)
+    def forward(ctx, kind, q, k, v, cu_q, cu_k, tiles, k_tiles, scale):
+        out, lse = globals()[kind.name](q, k, v, cu_q, cu_k, tiles, scale, want_lse=True)
         ctx.save_for_backward(q, k, v, out, lse, cu_q, cu_k, tiles, k_tiles)
-        ctx.scale = scale
+        ctx.kind, ctx.scale = kind, scale
         return out
 
     @staticmethod
     def backward(ctx, dout):
         q, k, v, out, lse, cu_q, cu_k, tiles, k_tiles = ctx.saved_tensors
-        dq, dk, dv = causal_attn_f16_bwd(q, k, v, out, lse, dout, cu_q, cu_k, tiles, k_tiles, ctx.scale)
-        return dq, dk, dv, None, None, None, None, None
+        dq, dk, dv = globals()[ctx.kind.name + "_bwd"](q, k, v, out, lse, dout, cu_q, cu_k, tiles, k_tiles, ctx.scale)
+        return None, dq, dk, dv, None, None, None, None, None
 
 
-def causal_attn_f16_train(q, k, v, cu_q, cu_k, tiles, k_tiles, scale):
-    """`causal_attn_f16` with a gradient: an autograd Function over (q, k, v), column-block views of the fused projection output
-    included.  Forward: `causal_attn_f16(..., want_lse=True)` (the same deterministic kernel, also when a checkpointed block
-    recomputes it); saved: q, k, v, out, lse and the lists; backward: ONE call of `causal_attn_f16_bwd` (dout of any stride: made
-    contiguous only if needed).  Returns out fp16 [Tq, nh * hd]."""
-    return _CausalAttnF16Train.apply(q, k, v, cu_q, cu_k, tiles, k_tiles, scale)
+def _causal_attn_train(kind, q, k, v, cu_q, cu_k, tiles, k_tiles, scale):
+    """The forward with a gradient: an autograd Function over (q, k, v), column-block views of the fused projection output
+    included.  Forward: the raw forward with want_lse=True (the same deterministic kernel, also when a checkpointed block
+    recomputes it); saved: q, k, v, out, lse and the lists; backward: ONE call of the raw backward (dout of any stride: made
+    contiguous only if needed).  Returns out [Tq, nh * hd]."""
+    return _CausalAttnTrain.apply(kind, q, k, v, cu_q, cu_k, tiles, k_tiles, scale)
+
+
+def _bind(impl, kind):
+    f = functools.partial(impl, kind)
+    f.__doc__ = f"`{impl.__name__}` on {str(kind.dtype)[6:]} storage.\n\n{impl.__doc__}"
+    return f
+
+
+causal_attn_f32_ok, causal_attn_f16_ok = _bind(_causal_attn_ok, _CAUSAL_F32), _bind(_causal_attn_ok, _CAUSAL_F16)
+causal_attn_f32, causal_attn_f16 = _bind(_causal_attn_fwd, _CAUSAL_F32), _bind(_causal_attn_fwd, _CAUSAL_F16)
+causal_attn_f32_bwd, causal_attn_f16_bwd = _bind(_causal_attn_bwd, _CAUSAL_F32), _bind(_causal_attn_bwd, _CAUSAL_F16)
+causal_attn_f32_train, causal_attn_f16_train = _bind(_causal_attn_train, _CAUSAL_F32), _bind(_causal_attn_train, _CAUSAL_F16)
+causal_attn_f16_shape_ok = causal_attn_f32_shape_ok
+causal_attn_f16_tile_list, causal_attn_f16_tile_table = causal_attn_f32_tile_list, causal_attn_f32_tile_table
+causal_attn_f16_key_tile_list, causal_attn_f16_key_tile_table = causal_attn_f32_key_tile_list, causal_attn_f32_key_tile_table
 
 
 def add_layernorm(a, b, weight, bias, eps, out=None):

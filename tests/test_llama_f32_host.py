@@ -111,6 +111,11 @@ def test_kernel_source_is_plain_hip():
     src = open(os.path.join(ROOT, "rankpo_amd", "csrc", "causal_attn_f32.hip")).read()
     code = "\n".join(line.split("//")[0] for line in src.splitlines())
     assert not re.search(r"\basm\b|__asm__|s_waitcnt|__builtin_amdgcn_s_waitcnt", code)
+    # what the four units share: held to the same rule
+    common = open(os.path.join(ROOT, "rankpo_amd", "csrc", "causal_attn_common.hpp")).read()
+    common = "\n".join(line.split("//")[0] for line in common.splitlines())
+    assert not re.search(r"\basm\b|__asm__|s_waitcnt|__builtin_amdgcn_s_waitcnt", common)
+    assert '#include "causal_attn_common.hpp"' in src
     assert "__builtin_amdgcn_mfma_f32_16x16x4f32" in code
     mk = open(os.path.join(ROOT, "rankpo_amd", "csrc", "Makefile")).read()
     assert re.search(r"^LLAMA_F32_SRCS := causal_attn_f32\.hip$", mk, re.M) and "$(LLAMA_F32_SRCS:.hip=.o)" in mk
