@@ -4302,6 +4302,41 @@ extern "C" int rpo_build_flags(void) {
 #endif
 }
 
+// the instantiation of fa_fwd128_kernel that rpo_flash_attn_fwd launches at head_dim 128 with 128-query entries; the -D overrides
+// are the ablation builds of profiles/r05_fa_fwd128_ablation.txt
+#ifndef RPO_F128_WQ
+#define RPO_F128_WQ 4
+#endif
+#ifndef RPO_F128_HEADS
+#define RPO_F128_HEADS 1
+#endif
+#ifndef RPO_F128_SUB
+#define RPO_F128_SUB 1
+#endif
+#ifndef RPO_F128_KF
+#define RPO_F128_KF false
+#endif
+#define RPO_F128_KERNEL fa_fwd128_kernel<RPO_F128_WQ, RPO_F128_HEADS, RPO_F128_SUB, RPO_F128_KF>
+
+// The argument rules that rpo_flash_attn_fwd and rpo_flash_attn_bwd share word for word.  Each entry calls them at its own place
+// among its other rules: which status answers an input with two faults follows from that order, and the order stays.
+// rope_cos / rope_sin come as a pair with a positive period (else INVALID_ARG) and 16-byte aligned (else UNSUPPORTED)
+static int fa_rope_status(const float* rope_cos, const float* rope_sin, int64_t rope_period) {
+    if ((rope_cos == nullptr) != (rope_sin == nullptr) || (rope_cos && rope_period <= 0)) return RPO_ERR_INVALID_ARG;
+    if (rope_cos && (!rpo_aligned16(rope_cos) || !rpo_aligned16(rope_sin))) return RPO_ERR_UNSUPPORTED;
+    return RPO_OK;
+}
+static bool fa_heads_ok(int64_t num_heads, int64_t num_kv_heads, int64_t head_dim) {
+    return (head_dim == kFaHD || head_dim == kFa128HD) && num_heads > 0 && num_kv_heads > 0 && num_heads % num_kv_heads == 0 &&
+           num_heads <= 65535;
+}
+// log2 of the q heads per kv head, rounded up: the one-wave dK/dV kernels index (slice, head) by shift / mask on the downward sweep
+static int fa_group_shift(int group) {
+    int shift = 0;
+    while ((1 << shift) < group) ++shift;
+    return shift;
+}
+
 extern "C" int rpo_flash_attn_fwd(const void* q, const void* k, const void* v, int64_t q_stride, int64_t k_stride,
                                   int64_t v_stride, const int* cu_seqlens, const int* tiles, int64_t ntiles,
                                   int64_t tile_cols, int64_t total_tokens, int64_t num_heads, int64_t num_kv_heads, int64_t head_dim,
@@ -4319,68 +4354,34 @@ extern "C" int rpo_flash_attn_fwd(const void* q, const void* k, const void* v, i
         return RPO_ERR_UNSUPPORTED;
     // rope_cos / rope_sin (both or neither): q arrives UN-rotated and is rotated IN PLACE by the block that owns it (k must
     // arrive rotated: every query block reads it)
-    if ((rope_cos == nullptr) != (rope_sin == nullptr) || (rope_cos && rope_period <= 0)) return RPO_ERR_INVALID_ARG;
-    if (rope_cos && (!rpo_aligned16(rope_cos) || !rpo_aligned16(rope_sin))) return RPO_ERR_UNSUPPORTED;
+    if (const int rc = fa_rope_status(rope_cos, rope_sin, rope_period)) return rc;
     if (!(tile_cols == 2 || (tile_cols == 3 && ntiles % 8 == 0))) return RPO_ERR_UNSUPPORTED;
-    if ((head_dim != kFaHD && head_dim != kFa128HD) || num_heads <= 0 || num_kv_heads <= 0 || num_heads % num_kv_heads != 0 ||
-        num_heads > 65535)
-        return RPO_ERR_UNSUPPORTED;
+    if (!fa_heads_ok(num_heads, num_kv_heads, head_dim)) return RPO_ERR_UNSUPPORTED;
     if (q_stride % 8 || k_stride % 8 || v_stride % 8 || out_stride % 4 || !rpo_aligned16(q) || !rpo_aligned16(k) ||
         !rpo_aligned16(v) || (reinterpret_cast<uintptr_t>(out) & 7))
         return RPO_ERR_UNSUPPORTED;
     if (q_block == 64 && (out_stride % 8 || !rpo_aligned16(out))) return RPO_ERR_UNSUPPORTED;      // whole-row stores, 16 bytes per lane
     hipStream_t st = (hipStream_t)stream;
     const float log2e = 1.4426950408889634f;
-    dim3 grid((unsigned)ntiles, tile_cols == 3 ? 1u : (unsigned)num_heads);
-#ifndef RPO_F128_WQ
-#define RPO_F128_WQ 4
-#endif
-#ifndef RPO_F128_HEADS
-#define RPO_F128_HEADS 1
-#endif
-#ifndef RPO_F128_SUB
-#define RPO_F128_SUB 1
-#endif
-#ifndef RPO_F128_KF
-#define RPO_F128_KF false
-#endif
-    if (head_dim == kFa128HD && tile_cols != 3) grid.y = (unsigned)(num_heads / RPO_F128_HEADS);
-#define RPO_F128_KERNEL fa_fwd128_kernel<RPO_F128_WQ, RPO_F128_HEADS, RPO_F128_SUB, RPO_F128_KF>
+    // every forward kernel takes the same arguments.  Grid: x = the entries; y = the launch's share of the heads, `heads` q heads
+    // per block (a three-column list names the head itself: y = 1)
+    auto launch = [&](auto kernel, int64_t heads, unsigned threads) {
+        const dim3 grid((unsigned)ntiles, tile_cols == 3 ? 1u : (unsigned)(num_heads / heads));
+        RPO_LAUNCH(kernel, grid, dim3(threads), 0, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, q_stride, k_stride,
+                   v_stride, cu_seqlens, tiles, (int)tile_cols, (int)num_heads, (int)num_kv_heads, scale * log2e, scale,
+                   (bf16_t*)out, out_stride, lse, lse_max_len > 0 ? num_heads * lse_max_len : 0,
+                   lse_max_len > 0 ? lse_max_len : total_tokens, lse_max_len > 0 ? 0 : 1, rope_cos, rope_sin, rope_period,
+                   (bf16_t*)const_cast<void*>(q));
+        return rpo_launch_status();
+    };
 #ifndef RPO_ONEWAVE64
     if (q_block == 64 && head_dim == kFaHD) return RPO_ERR_UNSUPPORTED;       // not in this build (make ONEWAVE64=1; rpo_build_flags())
 #else
-    if (q_block == 64 && head_dim == kFaHD) {
-        if (tile_cols != 3) grid.y = (unsigned)(num_heads / 4);
-        RPO_LAUNCH(fa_fwd64w_kernel, grid, dim3(256), 0, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, q_stride,
-                   k_stride, v_stride, cu_seqlens, tiles, (int)tile_cols, (int)num_heads, (int)num_kv_heads, scale * log2e, scale,
-                   (bf16_t*)out, out_stride, lse, lse_max_len > 0 ? num_heads * lse_max_len : 0,
-                   lse_max_len > 0 ? lse_max_len : total_tokens, lse_max_len > 0 ? 0 : 1, rope_cos, rope_sin, rope_period,
-                   (bf16_t*)const_cast<void*>(q));
-        return rpo_launch_status();
-    }
+    if (q_block == 64 && head_dim == kFaHD) return launch(fa_fwd64w_kernel, 4, 256);
 #endif
-    if (q_block == 64) {
-        if (tile_cols != 3) grid.y = (unsigned)(num_heads / 4);
-        RPO_LAUNCH(fa_fwd128w_kernel, grid, dim3(256), 0, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, q_stride,
-                   k_stride, v_stride, cu_seqlens, tiles, (int)tile_cols, (int)num_heads, (int)num_kv_heads, scale * log2e, scale,
-                   (bf16_t*)out, out_stride, lse, lse_max_len > 0 ? num_heads * lse_max_len : 0,
-                   lse_max_len > 0 ? lse_max_len : total_tokens, lse_max_len > 0 ? 0 : 1, rope_cos, rope_sin, rope_period,
-                   (bf16_t*)const_cast<void*>(q));
-        return rpo_launch_status();
-    }
-    if (head_dim == kFa128HD)
-        RPO_LAUNCH((RPO_F128_KERNEL), grid, dim3(64 * RPO_F128_WQ * RPO_F128_HEADS), 0, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, q_stride,
-                   k_stride, v_stride, cu_seqlens, tiles, (int)tile_cols, (int)num_heads, (int)num_kv_heads, scale * log2e, scale,
-                   (bf16_t*)out, out_stride, lse, lse_max_len > 0 ? num_heads * lse_max_len : 0,
-                   lse_max_len > 0 ? lse_max_len : total_tokens, lse_max_len > 0 ? 0 : 1, rope_cos, rope_sin, rope_period,
-                   (bf16_t*)const_cast<void*>(q));
-    else
-        RPO_LAUNCH(fa_fwd_kernel, grid, dim3(kFaThreads), 0, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, q_stride,
-                   k_stride, v_stride, cu_seqlens, tiles, (int)tile_cols, (int)num_heads, (int)num_kv_heads, scale * log2e, scale,
-                   (bf16_t*)out, out_stride, lse, lse_max_len > 0 ? num_heads * lse_max_len : 0,
-                   lse_max_len > 0 ? lse_max_len : total_tokens, lse_max_len > 0 ? 0 : 1, rope_cos, rope_sin, rope_period,
-                   (bf16_t*)const_cast<void*>(q));
-    return rpo_launch_status();
+    if (q_block == 64) return launch(fa_fwd128w_kernel, 4, 256);
+    if (head_dim == kFa128HD) return launch(RPO_F128_KERNEL, RPO_F128_HEADS, 64 * RPO_F128_WQ * RPO_F128_HEADS);
+    return launch(fa_fwd_kernel, 1, kFaThreads);
 }
 
 extern "C" int rpo_flash_attn_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout,
@@ -4405,17 +4406,15 @@ extern "C" int rpo_flash_attn_bwd(const void* q, const void* k, const void* v, c
 #endif
     // rope_cos / rope_sin (both or neither): dq / dk leave as gradients w.r.t. the PRE-rotary q / k (inverse rotation in the
     // epilogues); not offered by the 8-wave dK/dV kernel (key_block 64), whose epilogue splits a row's halves over two passes
-    if ((rope_cos == nullptr) != (rope_sin == nullptr) || (rope_cos && rope_period <= 0)) return RPO_ERR_INVALID_ARG;
-    if (rope_cos && (key_block == 64 || !rpo_aligned16(rope_cos) || !rpo_aligned16(rope_sin))) return RPO_ERR_UNSUPPORTED;
+    if (const int rc = fa_rope_status(rope_cos, rope_sin, rope_period)) return rc;
+    if (rope_cos && key_block == 64) return RPO_ERR_UNSUPPORTED;
     if (n_q_tiles <= 0 || n_k_tiles <= 0 || total_tokens <= 0) return RPO_ERR_INVALID_ARG;
     // `key_block` states what the entries of `k_tiles` mean: blocks of 256 keys (one-wave-per-SIMD dK/dV kernel) or of 64
     // keys (the 8-wave kernel).  The caller that built the table says so; nothing is read from the environment.
     // head_dim 128: blocks of 128 keys (fa_bwd_dkdv128_kernel), nothing else.
     if (head_dim == kFa128HD ? key_block != kD128Keys : (key_block != 256 && key_block != 64)) return RPO_ERR_UNSUPPORTED;
     if (!(q_tile_cols == 2 || (q_tile_cols == 3 && n_q_tiles % 8 == 0))) return RPO_ERR_UNSUPPORTED;
-    if ((head_dim != kFaHD && head_dim != kFa128HD) || num_heads <= 0 || num_kv_heads <= 0 || num_heads % num_kv_heads != 0 ||
-        num_heads > 65535)
-        return RPO_ERR_UNSUPPORTED;
+    if (!fa_heads_ok(num_heads, num_kv_heads, head_dim)) return RPO_ERR_UNSUPPORTED;
     if (q_stride % 8 || k_stride % 8 || v_stride % 8 || out_stride % 8 || dout_stride % 8 || dq_stride % 4 ||
         dk_stride % 4 || dv_stride % 4 || !rpo_aligned16(q) || !rpo_aligned16(k) || !rpo_aligned16(v) ||
         !rpo_aligned16(out) || !rpo_aligned16(dout))
@@ -4424,52 +4423,44 @@ extern "C" int rpo_flash_attn_bwd(const void* q, const void* k, const void* v, c
     const float log2e = 1.4426950408889634f;
     float* nd = delta;                                       // scratch [2][num_heads][T]: -delta | -lse / scale
     float* nl = delta + num_heads * total_tokens;
-    // (round 1 launched fa_delta_kernel here; the dQ kernel now computes and writes both row constants itself)
+    // the dQ kernels (they compute and write both row constants themselves: round 1 launched fa_delta_kernel here).  Grid as the
+    // forward's: `heads` q heads per block
+    auto launch_dq = [&](auto kernel, int64_t heads, unsigned threads) {
+        const dim3 grid((unsigned)n_q_tiles, q_tile_cols == 3 ? 1u : (unsigned)(num_heads / heads));
+        RPO_LAUNCH(kernel, grid, dim3(threads), 0, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout,
+                   q_stride, k_stride, v_stride, dout_stride, cu_seqlens, q_tiles, (int)q_tile_cols, (int)num_heads,
+                   (int)num_kv_heads, scale * log2e, scale, lse, (const bf16_t*)out, out_stride, nl, nd, total_tokens, (bf16_t*)dq,
+                   dq_stride, rope_cos, rope_sin, rope_period);
+        return rpo_launch_status();
+    };
+    const int rc = head_dim == kFa128HD ? launch_dq(fa_bwd_dq128_kernel, 1, kFaThreads)
+#ifdef RPO_ONEWAVE64
+                   : q_block == 64      ? launch_dq(fa_bwd_dq64w_kernel, 4, 256)
+#endif
+                                        : launch_dq(fa_bwd_dq_kernel, 1, kFaThreads);
+    if (rc != RPO_OK) return rc;
+    // the dK/dV kernels: one block per entry of k_tiles, the grid rounded up to the 8 XCDs
+    const dim3 dkdv_grid((unsigned)(((n_k_tiles + 7) / 8) * 8));
+    // the one-wave-per-SIMD kernels (256 keys at head_dim 64, 128 keys at head_dim 128).  The downward sweep indexes (slice, head)
+    // by shift / mask: a group that is not a power of two keeps the ascending order
+    const int group = (int)(num_heads / num_kv_heads), gshift = fa_group_shift(group);
+    const bool down = sweep_down && (1 << gshift) == group;
+    auto launch_dkdv = [&](auto kernel, int lds) {
+        RPO_LAUNCH(kernel, dkdv_grid, dim3(256), lds, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout,
+                   q_stride, k_stride, v_stride, dout_stride, cu_seqlens, k_tiles, (int)num_heads, (int)num_kv_heads, scale * log2e,
+                   scale, nl, nd, total_tokens, (bf16_t*)dk, (bf16_t*)dv, dk_stride, dv_stride, (int)n_k_tiles, gshift, rope_cos,
+                   rope_sin, rope_period);
+        return rpo_launch_status();
+    };
     if (head_dim == kFa128HD) {
-        RPO_LAUNCH(fa_bwd_dq128_kernel, dim3((unsigned)n_q_tiles, q_tile_cols == 3 ? 1u : (unsigned)num_heads), dim3(kFaThreads),
-                   0, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout, q_stride, k_stride, v_stride,
-                   dout_stride, cu_seqlens, q_tiles, (int)q_tile_cols, (int)num_heads, (int)num_kv_heads, scale * log2e, scale,
-                   lse, (const bf16_t*)out, out_stride, nl, nd, total_tokens, (bf16_t*)dq, dq_stride, rope_cos, rope_sin, rope_period);
-        const int rc128 = rpo_launch_status();
-        if (rc128 != RPO_OK) return rc128;
         static const bool attr128_set = [] {
             (void)hipFuncSetAttribute((const void*)fa_bwd_dkdv128_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kD128Lds);
             (void)hipFuncSetAttribute((const void*)fa_bwd_dkdv128_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kD128Lds);
             return true;
         }();
         (void)attr128_set;
-        const int group128 = (int)(num_heads / num_kv_heads);
-        int gshift128 = 0;
-        while ((1 << gshift128) < group128) ++gshift128;
-        const dim3 grid128((unsigned)(((n_k_tiles + 7) / 8) * 8));
-        if (sweep_down && (1 << gshift128) == group128)
-            RPO_LAUNCH(fa_bwd_dkdv128_kernel<true>, grid128, dim3(256), kD128Lds, st, (const bf16_t*)q, (const bf16_t*)k,
-                       (const bf16_t*)v, (const bf16_t*)dout, q_stride, k_stride, v_stride, dout_stride, cu_seqlens, k_tiles,
-                       (int)num_heads, (int)num_kv_heads, scale * log2e, scale, nl, nd, total_tokens, (bf16_t*)dk, (bf16_t*)dv,
-                       dk_stride, dv_stride, (int)n_k_tiles, gshift128, rope_cos, rope_sin, rope_period);
-        else
-            RPO_LAUNCH(fa_bwd_dkdv128_kernel<false>, grid128, dim3(256), kD128Lds, st, (const bf16_t*)q, (const bf16_t*)k,
-                       (const bf16_t*)v, (const bf16_t*)dout, q_stride, k_stride, v_stride, dout_stride, cu_seqlens, k_tiles,
-                       (int)num_heads, (int)num_kv_heads, scale * log2e, scale, nl, nd, total_tokens, (bf16_t*)dk, (bf16_t*)dv,
-                       dk_stride, dv_stride, (int)n_k_tiles, gshift128, rope_cos, rope_sin, rope_period);
-        return rpo_launch_status();
+        return down ? launch_dkdv(fa_bwd_dkdv128_kernel<true>, kD128Lds) : launch_dkdv(fa_bwd_dkdv128_kernel<false>, kD128Lds);
     }
-#ifdef RPO_ONEWAVE64
-    if (q_block == 64)
-        RPO_LAUNCH(fa_bwd_dq64w_kernel, dim3((unsigned)n_q_tiles, q_tile_cols == 3 ? 1u : (unsigned)(num_heads / 4)), dim3(256), 0,
-                   st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout, q_stride, k_stride, v_stride,
-                   dout_stride, cu_seqlens, q_tiles, (int)q_tile_cols, (int)num_heads, (int)num_kv_heads, scale * log2e, scale, lse,
-                   (const bf16_t*)out, out_stride, nl, nd, total_tokens, (bf16_t*)dq, dq_stride, rope_cos, rope_sin, rope_period);
-    else
-#endif
-        RPO_LAUNCH(fa_bwd_dq_kernel, dim3((unsigned)n_q_tiles, q_tile_cols == 3 ? 1u : (unsigned)num_heads), dim3(kFaThreads), 0,
-                   st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout, q_stride, k_stride, v_stride,
-                   dout_stride, cu_seqlens, q_tiles, (int)q_tile_cols, (int)num_heads, (int)num_kv_heads, scale * log2e, scale, lse,
-                   (const bf16_t*)out, out_stride, nl, nd, total_tokens, (bf16_t*)dq, dq_stride, rope_cos, rope_sin, rope_period);
-    int rc = rpo_launch_status();
-    if (rc != RPO_OK) return rc;
-    const unsigned dkdv_grid = (unsigned)(((n_k_tiles + 7) / 8) * 8);
-    const bool use_v1 = key_block == 64;
 #ifdef RPO_D4_EXP_DQ_ATOMICS
     {
         static float* exp_buf = nullptr;                       // experiment only: one buffer for the largest batch the tools use
@@ -4487,26 +4478,12 @@ extern "C" int rpo_flash_attn_bwd(const void* q, const void* k, const void* v, c
         return true;
     }();
     (void)attr_set;
-    if (use_v1) {
-        RPO_LAUNCH(fa_bwd_dkdv_kernel, dim3(dkdv_grid), dim3(kFaDkdvThreads), kDmaLds, st, (const bf16_t*)q, (const bf16_t*)k,
+    if (key_block == 64) {                                   // the 8-wave kernel: no sweep order, no rotary epilogue
+        RPO_LAUNCH(fa_bwd_dkdv_kernel, dkdv_grid, dim3(kFaDkdvThreads), kDmaLds, st, (const bf16_t*)q, (const bf16_t*)k,
                    (const bf16_t*)v, (const bf16_t*)dout, q_stride, k_stride, v_stride, dout_stride, cu_seqlens, k_tiles,
                    (int)num_heads, (int)num_kv_heads, scale * log2e, scale, nl, nd, total_tokens, (bf16_t*)dk,
                    (bf16_t*)dv, dk_stride, dv_stride, (int)n_k_tiles);
-    } else {
-        const int group = (int)(num_heads / num_kv_heads);
-        int gshift = 0;
-        while ((1 << gshift) < group) ++gshift;
-        // the downward sweep indexes (slice, head) by shift / mask: a group that is not a power of two keeps the ascending order
-        if (sweep_down && (1 << gshift) == group)
-            RPO_LAUNCH(fa_bwd_dkdv4_kernel<true>, dim3(dkdv_grid), dim3(256), kDkdv4Lds, st, (const bf16_t*)q, (const bf16_t*)k,
-                       (const bf16_t*)v, (const bf16_t*)dout, q_stride, k_stride, v_stride, dout_stride, cu_seqlens, k_tiles,
-                       (int)num_heads, (int)num_kv_heads, scale * log2e, scale, nl, nd, total_tokens, (bf16_t*)dk,
-                       (bf16_t*)dv, dk_stride, dv_stride, (int)n_k_tiles, gshift, rope_cos, rope_sin, rope_period);
-        else
-            RPO_LAUNCH(fa_bwd_dkdv4_kernel<false>, dim3(dkdv_grid), dim3(256), kDkdv4Lds, st, (const bf16_t*)q, (const bf16_t*)k,
-                       (const bf16_t*)v, (const bf16_t*)dout, q_stride, k_stride, v_stride, dout_stride, cu_seqlens, k_tiles,
-                       (int)num_heads, (int)num_kv_heads, scale * log2e, scale, nl, nd, total_tokens, (bf16_t*)dk,
-                       (bf16_t*)dv, dk_stride, dv_stride, (int)n_k_tiles, gshift, rope_cos, rope_sin, rope_period);
+        return rpo_launch_status();
     }
-    return rpo_launch_status();
+    return down ? launch_dkdv(fa_bwd_dkdv4_kernel<true>, kDkdv4Lds) : launch_dkdv(fa_bwd_dkdv4_kernel<false>, kDkdv4Lds);
 }

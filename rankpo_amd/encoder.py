@@ -430,32 +430,32 @@ class LlamaAttention(nn.Module):
         nq, nk = self.nh * self.hd, self.nkv * self.hd
         qkv = self._fused(x, (self.q_proj, self.k_proj, self.v_proj))            # [N, L, nq + 2 nk]
         fused = _ops.fused_encoder_ops_ok(x, self.hd)
-        if (isinstance(attn_mask, VarlenCtx) and fused and attn_mask.k_tiles is not None and self.hd in (64, 128)
-                and x.dtype == torch.bfloat16 and FOLD_ROPE):
+        # the hand-written bf16 flash attention on the column blocks of the packed projection output
+        hand = isinstance(attn_mask, VarlenCtx) and fused and self.hd in (64, 128) and x.dtype == torch.bfloat16
+        o = None
+        if hand and attn_mask.k_tiles is not None and FOLD_ROPE:
             # training on packed tokens: rotary + attention as one autograd node -- the rotary pass runs in place on the
             # projection output, attention reads q / k / v as its column blocks, and the backward writes ONE d(q|k|v)
             # buffer (no split / cat copies) with the inverse rotation already applied in the dQ / dK epilogues
             o = _ops.rope_flash_attn_varlen_qkv(qkv, rope.cos32, rope.sin32, self.nh, self.nkv, attn_mask.cu,
                                                 attn_mask.tiles, attn_mask.k_tiles, 1.0 / math.sqrt(self.hd), head_dim=self.hd,
                                                 fold_forward=FOLD_ROPE >= 2, fwd_tiles=attn_mask.fwd_tiles)
-            return _ops.linear(o.reshape(1, L, self.nh * self.hd), self.o_proj.weight, self.o_proj.bias)
-        if (isinstance(attn_mask, VarlenCtx) and fused and attn_mask.tiles is not None and self.hd in (64, 128)
-                and x.dtype == torch.bfloat16 and FOLD_ROPE and not torch.is_grad_enabled()):
+        elif hand and attn_mask.tiles is not None and FOLD_ROPE and not torch.is_grad_enabled():
             # no-grad callers (ModelForInference.encode, the RankPO ref_model under inference_mode, eval-mode scoring): the same
             # rotary fold and forward kernel, without a key-block table, an autograd node or row statistics
             o = _ops.rope_flash_attn_varlen_qkv_fwd(qkv, rope.cos32, rope.sin32, self.nh, self.nkv, attn_mask.cu, attn_mask.tiles,
                                                     1.0 / math.sqrt(self.hd), head_dim=self.hd, fwd_tiles=attn_mask.fwd_tiles)
-            return F.linear(o.reshape(1, L, self.nh * self.hd), self.o_proj.weight, self.o_proj.bias)
-        if fused:       # one in-place HIP pass over the q and k heads instead of neg / cat / 2 mul / add per tensor
-            qkv = _ops.rope_(qkv, rope.cos32, rope.sin32, self.nh + self.nkv, self.hd, grad_inplace=True)
-        q, k, v = qkv.split([nq, nk, nk], dim=-1)
-        if (isinstance(attn_mask, VarlenCtx) and fused and attn_mask.k_tiles is not None and self.hd in (64, 128)
-                and x.dtype == torch.bfloat16):
-            # A/B arm (FOLD_ROPE = False): the rotary pass and the attention as two autograd nodes
-            o = _ops.flash_attn_varlen_qkv(qkv.view(L, -1), self.nh, self.nkv, attn_mask.cu, attn_mask.tiles,
-                                           attn_mask.k_tiles, 1.0 / math.sqrt(self.hd), head_dim=self.hd,
-                                           fwd_tiles=attn_mask.fwd_tiles)
+        else:
+            if fused:   # one in-place HIP pass over the q and k heads instead of neg / cat / 2 mul / add per tensor
+                qkv = _ops.rope_(qkv, rope.cos32, rope.sin32, self.nh + self.nkv, self.hd, grad_inplace=True)
+            if hand and attn_mask.k_tiles is not None:
+                # A/B arm (FOLD_ROPE = False): the rotary pass and the attention as two autograd nodes
+                o = _ops.flash_attn_varlen_qkv(qkv.view(L, -1), self.nh, self.nkv, attn_mask.cu, attn_mask.tiles,
+                                               attn_mask.k_tiles, 1.0 / math.sqrt(self.hd), head_dim=self.hd,
+                                               fwd_tiles=attn_mask.fwd_tiles)
+        if o is not None:       # (`ops.linear` is F.linear under no-grad)
             return _ops.linear(o.reshape(1, L, self.nh * self.hd), self.o_proj.weight, self.o_proj.bias)
+        q, k, v = qkv.split([nq, nk, nk], dim=-1)
         if isinstance(attn_mask, VarlenCtx):
             # packed tokens [1, T, d]: variable-length causal flash attention, no pad tokens anywhere
             q, k, v = q.view(L, self.nh, self.hd), k.view(L, self.nkv, self.hd), v.view(L, self.nkv, self.hd)
@@ -525,27 +525,25 @@ class LlamaLayer(nn.Module):
         kv = att._fused(h, (att.k_proj, att.v_proj))                         # [1, T, 2 nk]
         q = att.q_proj(h[0].index_select(0, last_idx))                       # [N, nh*hd]
         rope_last = rope.select(last_idx)
-        if _ops.fused_encoder_ops_ok(x, att.hd):
+        fused = _ops.fused_encoder_ops_ok(x, att.hd)
+        if fused:
             q = _ops.rope_(q, rope_last.cos32, rope_last.sin32, att.nh, att.hd)
             kv = _ops.rope_(kv, rope.cos32, rope.sin32, att.nkv, att.hd, grad_inplace=True)   # rotates the k heads only
-            q = q.view(-1, att.nh, att.hd)
-            if ctx.tiles is not None and _ops.last_query_attn_ok(q, kv, att.nh, att.nkv, att.hd):
-                # hand-written one-query-per-sequence attention on the fused k|v buffer (ctx.tiles: hand_attention is on)
-                o = _ops.last_query_attn(q, kv, ctx.cu, att.nkv, att.hd, 1.0 / math.sqrt(att.hd))
-                xl = x[0].index_select(0, last_idx) + att.o_proj(o.reshape(-1, att.nh * att.hd))
-                # last_in_block: only the residual add follows, and an add saves nothing for backward
-                return xl + self.mlp(_norm_rows(xl, self.post_attention_layernorm), last_in_block=True)
-            k, v = kv.split([nk, nk], dim=-1)
-            k = k.view(T, att.nkv, att.hd)
+        q = q.view(-1, att.nh, att.hd)
+        if fused and ctx.tiles is not None and _ops.last_query_attn_ok(q, kv, att.nh, att.nkv, att.hd):
+            # hand-written one-query-per-sequence attention on the fused k|v buffer (ctx.tiles: hand_attention is on)
+            o = _ops.last_query_attn(q, kv, ctx.cu, att.nkv, att.hd, 1.0 / math.sqrt(att.hd))
         else:
             k, v = kv.split([nk, nk], dim=-1)
-            q, k = q.view(-1, att.nh, att.hd), k.view(T, att.nkv, att.hd)
-            cq, sq = rope_last.full(x.dtype, packed=True)
-            ck, sk = rope.full(x.dtype, packed=True)
-            q = q * cq + _rotate_half(q) * sq
-            k = k * ck + _rotate_half(k) * sk
-        o = _varlen_last_query_attention(q, k, v.view(T, att.nkv, att.hd), ctx)
+            k = k.view(T, att.nkv, att.hd)
+            if not fused:
+                cq, sq = rope_last.full(x.dtype, packed=True)
+                ck, sk = rope.full(x.dtype, packed=True)
+                q = q * cq + _rotate_half(q) * sq
+                k = k * ck + _rotate_half(k) * sk
+            o = _varlen_last_query_attention(q, k, v.view(T, att.nkv, att.hd), ctx)
         xl = x[0].index_select(0, last_idx) + att.o_proj(o.reshape(-1, att.nh * att.hd))
+        # last_in_block: only the residual add follows, and an add saves nothing for backward
         return xl + self.mlp(_norm_rows(xl, self.post_attention_layernorm), last_in_block=True)
 
 
@@ -785,9 +783,8 @@ class LlamaEncoder(nn.Module):
                 fwd_tiles = _ops.attn_fwd_tile_table(lens, x.device, self.config.num_attention_heads,
                                                      self.config.num_key_value_heads, self.config.head_dim)
             if torch.is_grad_enabled():
-                k_tiles = _ops.attn_key_tile_table(
-                    lens, x.device, self.config.num_key_value_heads,
-                    _ops.ATTN_KEY_BLOCK if self.config.head_dim == 64 else _ops.ATTN_KEY_BLOCK_HD128)
+                k_tiles = _ops.attn_key_tile_table(lens, x.device, self.config.num_key_value_heads,
+                                                   _ops.attn_key_block(self.config.head_dim))
         ctx = VarlenCtx(cu, lens, max(lens), tiles, k_tiles, fwd_tiles)
         native = _native_attention_lists(self, x.dtype, lens, x.device) if x.is_cuda else {}
         for name, table in native.items():

@@ -757,6 +757,16 @@ def _check_rope_tables(rope, hd, who):
         raise ValueError(f"{who}: rope must be (cos, sin), contiguous f32 [period, head_dim / 2]")
 
 
+def _rope_args(rope):
+    """(cos pointer, sin pointer, period) of the C entries' rope arguments; rope = (cos, sin) or None."""
+    return (None, None, 0) if rope is None else (rope[0].data_ptr(), rope[1].data_ptr(), rope[0].shape[0])
+
+
+def _fwd_work(tiles, fwd_tiles):
+    """(work list, its q_block) of the forward: its own list of 64-query entries where it has one, else the 128-row list."""
+    return (tiles, 128) if fwd_tiles is None else (fwd_tiles, 64)
+
+
 def flash_attn_varlen_fwd(q, k, v, cu_seqlens, tiles, scale, padded_lse_len: int = 0, num_seqs: int = 0, rope=None, q_block: int = 128,
                           want_lse: bool = True):
     """q [T, nh, hd], k / v [T, nkv, hd], hd = 64 or 128 (last two dims contiguous, token stride free); returns
@@ -783,10 +793,7 @@ def flash_attn_varlen_fwd(q, k, v, cu_seqlens, tiles, scale, padded_lse_len: int
     with torch.cuda.device(q.device):
         check(lib.rpo_flash_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(0), k.stride(0), v.stride(0),
                                      cu_seqlens.data_ptr(), tiles.data_ptr(), tiles.shape[0], tiles.shape[1], T, nh, nkv, hd, scale,
-                                     out.data_ptr(), nh * hd, _p(lse), padded_lse_len,
-                                     rope[0].data_ptr() if rope is not None else None,
-                                     rope[1].data_ptr() if rope is not None else None,
-                                     rope[0].shape[0] if rope is not None else 0, q_block, _stream(q)),
+                                     out.data_ptr(), nh * hd, _p(lse), padded_lse_len, *_rope_args(rope), q_block, _stream(q)),
               "rpo_flash_attn_fwd")
     return out, lse
 
@@ -803,6 +810,11 @@ ATTN_KEY_BLOCK = 256     # keys per entry of the dK/dV work list (256: one-wave-
 ATTN_SWEEP_DOWN = False
 ATTN_SWEEP_DOWN_HD128 = True
 ATTN_GROUP_TAIL = 0.0          # fraction of every XCD's work that runs heaviest-first BEHIND the group-ordered part (0: pure group order)
+
+
+def attn_key_block(head_dim: int) -> int:
+    """The keys per entry of the dK/dV work list that a head_dim (64 or 128) takes by default; read from the switches at call time."""
+    return ATTN_KEY_BLOCK if head_dim == 64 else ATTN_KEY_BLOCK_HD128
 
 
 def attn_key_tile_table(lens, device, num_kv_heads: int, block_n: int = ATTN_KEY_BLOCK, group_order=None):
@@ -899,10 +911,7 @@ def flash_attn_varlen_bwd(q, k, v, out, dout, lse, cu_seqlens, q_tiles, k_tiles,
                                      cu_seqlens.data_ptr(), q_tiles.data_ptr(), q_tiles.shape[0], q_tiles.shape[1], k_tiles.data_ptr(),
                                      k_tiles.shape[0], key_block, int(bool(sweep_down)), T, nh, nkv, hd, scale, lse.data_ptr(), delta.data_ptr(),
                                      dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), dq.stride(0), dk.stride(0), dv.stride(0),
-                                     rope[0].data_ptr() if rope is not None else None,
-                                     rope[1].data_ptr() if rope is not None else None,
-                                     rope[0].shape[0] if rope is not None else 0, q_block,
-                                     _stream(q)), "rpo_flash_attn_bwd")
+                                     *_rope_args(rope), q_block, _stream(q)), "rpo_flash_attn_bwd")
     return dq, dk, dv
 
 
@@ -914,9 +923,9 @@ class _FlashAttnVarlen(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, cu, tiles, k_tiles, max_len, scale, key_block, fwd_tiles=None):
         own_bwd = k_tiles is not None
-        out, lse = flash_attn_varlen_fwd(q, k, v, cu, tiles if fwd_tiles is None else fwd_tiles, scale,
-                                         padded_lse_len=0 if own_bwd else max_len, num_seqs=cu.numel() - 1,
-                                         q_block=128 if fwd_tiles is None else 64)
+        work, q_block = _fwd_work(tiles, fwd_tiles)
+        out, lse = flash_attn_varlen_fwd(q, k, v, cu, work, scale, padded_lse_len=0 if own_bwd else max_len,
+                                         num_seqs=cu.numel() - 1, q_block=q_block)
         ctx.save_for_backward(q, k, v, out, lse, cu, tiles, k_tiles if own_bwd else cu)
         ctx.meta = (max_len, scale, own_bwd, key_block)
         return out
@@ -937,85 +946,76 @@ class _FlashAttnVarlen(torch.autograd.Function):
 def flash_attn_varlen(q, k, v, cu, tiles, max_len, scale, k_tiles=None, key_block: int = ATTN_KEY_BLOCK, fwd_tiles=None):
     if not (torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad)):
         # nothing will differentiate this: the forward kernel alone, no row statistics (no padded zero-filled lse per layer)
-        return flash_attn_varlen_fwd(q, k, v, cu, tiles if fwd_tiles is None else fwd_tiles, scale, want_lse=False,
-                                     q_block=128 if fwd_tiles is None else 64)[0]
+        work, q_block = _fwd_work(tiles, fwd_tiles)
+        return flash_attn_varlen_fwd(q, k, v, cu, work, scale, want_lse=False, q_block=q_block)[0]
     return _FlashAttnVarlen.apply(q, k, v, cu, tiles, k_tiles, max_len, scale, key_block, fwd_tiles)
 
 
+def _qkv_views(x, nh, nkv, hd):
+    """The q | k | v column blocks of a fused buffer x [T, (nh + 2 nkv) * hd] as [T, heads, hd] views."""
+    nq, nk = nh * hd, nkv * hd
+    return (x[:, :nq].unflatten(1, (nh, hd)), x[:, nq:nq + nk].unflatten(1, (nkv, hd)),
+            x[:, nq + nk:].unflatten(1, (nkv, hd)))
+
+
+def _rope_heads_(x, cos, sin, head0, heads, hd):
+    """`rpo_rope` in place on the heads [head0, head0 + heads) of every row of a fused buffer x [T, W]."""
+    ptr = x.data_ptr() + head0 * hd * x.element_size()
+    with torch.cuda.device(x.device):
+        check(_lib.load().rpo_rope(ptr, ptr, x.shape[1], cos.data_ptr(), sin.data_ptr(), x.shape[0], heads, hd, cos.shape[0],
+                                   _dt(x), 0, _stream(x)), "rpo_rope")
+
+
+def _check_qkv(who, qkv, nh, nkv, hd, flat: bool = False):
+    """head_dim 64 / 128 and a contiguous fused buffer of that width; flat: exactly [T, W], else leading dims are allowed."""
+    if hd not in (64, 128):
+        raise ValueError(f"{who}: head_dim must be 64 or 128")
+    if (flat and qkv.dim() != 2) or qkv.shape[-1] != (nh + 2 * nkv) * hd or not qkv.is_contiguous():
+        raise ValueError(f"{who}: qkv must be a contiguous [{'' if flat else '..., '}T, (nh + 2 nkv) * head_dim] tensor")
+
+
 class _FlashAttnVarlenQKV(torch.autograd.Function):
-    """Same attention on the output of ONE fused q|k|v projection, [T, (nh + 2 nkv) * hd] (rotary already applied; hd = 64 or
-    128): the kernels read q / k / v as strided column blocks and the backward writes dq / dk / dv straight into the column
-    blocks of one d(q|k|v) buffer, which is the operand of the projection's gradient GEMMs (no split / cat copies: the cat
-    moved 1.6 GB per block on the cfg-2 passage tower)."""
+    """Same attention on the output of ONE fused q|k|v projection, [T, (nh + 2 nkv) * hd] (hd = 64 or 128): the kernels read
+    q / k / v as strided column blocks and the backward writes dq / dk / dv straight into the column blocks of one d(q|k|v)
+    buffer, which is the operand of the projection's gradient GEMMs (no split / cat copies: the cat moved 1.6 GB per block on the
+    cfg-2 passage tower).  cos / sin None: `qkv` arrives rotated.  cos / sin given: rotary embedding + attention as ONE autograd
+    node on the FRESH projection output: forward = `rpo_rope` in place on its q and k heads, or with fold_forward on its k heads
+    only, then the attention forward, which rotates (and writes back) the q block it loads anyway; backward = the attention
+    backward with the INVERSE rotation folded into the dQ / dK epilogues (f32, before the one rounding to bf16), so d(q|k|v) comes
+    back w.r.t. the pre-rotary projection output and no separate pass re-reads and re-rounds the q / k gradient (0.28 ms per block
+    on cfg 2); the rotated buffer is the node's second output."""
 
     @staticmethod
-    def _views(x, nh, nkv, hd):
-        nq, nk = nh * hd, nkv * hd
-        return (x[:, :nq].unflatten(1, (nh, hd)), x[:, nq:nq + nk].unflatten(1, (nkv, hd)),
-                x[:, nq + nk:].unflatten(1, (nkv, hd)))
-
-    @staticmethod
-    def forward(ctx, qkv, nh, nkv, cu, tiles, k_tiles, scale, key_block, fwd_tiles=None):
-        hd = qkv.shape[1] // (nh + 2 * nkv)
-        q, k, v = _FlashAttnVarlenQKV._views(qkv, nh, nkv, hd)
-        out, lse = flash_attn_varlen_fwd(q, k, v, cu, tiles if fwd_tiles is None else fwd_tiles, scale, padded_lse_len=0,
-                                         num_seqs=cu.numel() - 1, q_block=128 if fwd_tiles is None else 64)
-        ctx.save_for_backward(qkv, out, lse, cu, tiles, k_tiles)
-        ctx.meta = (nh, nkv, hd, scale, key_block)
-        return out
-
-    @staticmethod
-    def backward(ctx, go):
-        qkv, out, lse, cu, tiles, k_tiles = ctx.saved_tensors
-        nh, nkv, hd, scale, key_block = ctx.meta
-        q, k, v = _FlashAttnVarlenQKV._views(qkv, nh, nkv, hd)
-        dqkv = torch.empty_like(qkv)
-        flash_attn_varlen_bwd(q, k, v, out, go, lse, cu, tiles, k_tiles, scale,
-                              grads=_FlashAttnVarlenQKV._views(dqkv, nh, nkv, hd), key_block=key_block)
-        return dqkv, None, None, None, None, None, None, None, None
-
-
-class _RopeFlashAttnVarlenQKV(torch.autograd.Function):
-    """Rotary embedding + the attention of `_FlashAttnVarlenQKV` as ONE autograd node: forward = `rpo_rope` in place on the k heads
-    of the fresh projection output, then the attention forward, which rotates (and writes back) the q block it loads anyway; backward = the attention backward with the INVERSE rotation
-    folded into the dQ / dK epilogues (f32, before the one rounding to bf16), so d(q|k|v) comes back w.r.t. the pre-rotary
-    projection output and no separate pass re-reads and re-rounds the q / k gradient (0.28 ms per block on cfg 2)."""
-
-    @staticmethod
-    def forward(ctx, qkv, cos, sin, nh, nkv, cu, tiles, k_tiles, scale, key_block, fold_forward, fwd_tiles=None):
+    def forward(ctx, qkv, cos, sin, nh, nkv, cu, tiles, k_tiles, scale, key_block, fold_forward=False, fwd_tiles=None):
         x = qkv.view(-1, qkv.shape[-1])                      # [T, W]; `qkv` itself may carry leading batch dims ([1, T, W])
         hd = x.shape[1] // (nh + 2 * nkv)
-        lib = _lib.load()
-        # fold_forward: the rotary pass covers the k heads only (column block [nh hd, (nh + nkv) hd)): q is rotated by the
-        # attention forward itself, by the block that owns it (flash_attn_varlen_fwd's `rope`)
-        ptr = x.data_ptr() + (nh * hd * x.element_size() if fold_forward else 0)
-        with torch.cuda.device(x.device):
-            check(lib.rpo_rope(ptr, ptr, x.shape[1], cos.data_ptr(), sin.data_ptr(), x.shape[0],
-                               nkv if fold_forward else nh + nkv, hd, cos.shape[0], _dt(x), 0, _stream(x)), "rpo_rope")
-        # autograd wants a tensor modified in place among the outputs, and it must not be a view made outside (hence the
-        # caller's own tensor, not a reshaped view of it)
-        ctx.mark_dirty(qkv)
-        ctx.set_materialize_grads(False)
-        q, k, v = _FlashAttnVarlenQKV._views(x, nh, nkv, hd)
-        out, lse = flash_attn_varlen_fwd(q, k, v, cu, tiles if fwd_tiles is None else fwd_tiles, scale, padded_lse_len=0,
-                                         num_seqs=cu.numel() - 1, rope=(cos, sin) if fold_forward else None,
-                                         q_block=128 if fwd_tiles is None else 64)
-        ctx.save_for_backward(qkv, out, lse, cu, tiles, k_tiles, cos, sin)
+        rope = None if cos is None else (cos, sin)
+        if rope is not None:
+            # fold_forward: the rotary pass covers the k heads only (column block [nh hd, (nh + nkv) hd)): q is rotated by the
+            # attention forward itself, by the block that owns it (flash_attn_varlen_fwd's `rope`)
+            _rope_heads_(x, cos, sin, nh if fold_forward else 0, nkv if fold_forward else nh + nkv, hd)
+            # autograd wants a tensor modified in place among the outputs, and it must not be a view made outside (hence the
+            # caller's own tensor, not a reshaped view of it)
+            ctx.mark_dirty(qkv)
+            ctx.set_materialize_grads(False)
+        work, q_block = _fwd_work(tiles, fwd_tiles)
+        out, lse = flash_attn_varlen_fwd(*_qkv_views(x, nh, nkv, hd), cu, work, scale, padded_lse_len=0, num_seqs=cu.numel() - 1,
+                                         rope=rope if fold_forward else None, q_block=q_block)
+        ctx.save_for_backward(qkv, out, lse, cu, tiles, k_tiles, *(rope or ()))
         ctx.meta = (nh, nkv, hd, scale, key_block)
-        return out, qkv
+        return out if rope is None else (out, qkv)
 
     @staticmethod
-    def backward(ctx, go, g_rotated):
+    def backward(ctx, go, g_rotated=None):
         if g_rotated is not None:
             raise RuntimeError("rope_flash_attn_varlen_qkv: the rotated q|k|v buffer is internal, nothing may use it downstream")
-        qkv, out, lse, cu, tiles, k_tiles, cos, sin = ctx.saved_tensors
+        qkv, out, lse, cu, tiles, k_tiles, *rope = ctx.saved_tensors
         nh, nkv, hd, scale, key_block = ctx.meta
-        q, k, v = _FlashAttnVarlenQKV._views(qkv.view(-1, qkv.shape[-1]), nh, nkv, hd)
+        W = qkv.shape[-1]
         dqkv = torch.empty_like(qkv)
-        flash_attn_varlen_bwd(q, k, v, out, go, lse, cu, tiles, k_tiles, scale,
-                              grads=_FlashAttnVarlenQKV._views(dqkv.view(-1, qkv.shape[-1]), nh, nkv, hd), key_block=key_block,
-                              rope=(cos, sin))
-        return dqkv, None, None, None, None, None, None, None, None, None, None, None
+        flash_attn_varlen_bwd(*_qkv_views(qkv.view(-1, W), nh, nkv, hd), out, go, lse, cu, tiles, k_tiles, scale,
+                              grads=_qkv_views(dqkv.view(-1, W), nh, nkv, hd), key_block=key_block, rope=tuple(rope) or None)
+        return (dqkv,) + (None,) * 11
 
 
 def rope_flash_attn_varlen_qkv(qkv, cos, sin, num_heads, num_kv_heads, cu, tiles, k_tiles, scale, key_block=None,
@@ -1024,16 +1024,13 @@ def rope_flash_attn_varlen_qkv(qkv, cos, sin, num_heads, num_kv_heads, cu, tiles
     allowed: [1, T, W]; pass the projection's own tensor, not a reshaped view of it) bf16, contiguous, NOT yet rotated (it is
     rotated in place here); cos / sin: f32 [period, head_dim / 2] (row t % period for token t) -> attention
     output [T, num_heads, head_dim].  The gradient that comes back is w.r.t. the un-rotated projection output."""
-    if head_dim not in (64, 128):
-        raise ValueError("rope_flash_attn_varlen_qkv: head_dim must be 64 or 128")
-    if qkv.shape[-1] != (num_heads + 2 * num_kv_heads) * head_dim or not qkv.is_contiguous():
-        raise ValueError("rope_flash_attn_varlen_qkv: qkv must be a contiguous [..., T, (nh + 2 nkv) * head_dim] tensor")
+    _check_qkv("rope_flash_attn_varlen_qkv", qkv, num_heads, num_kv_heads, head_dim)
     if key_block is None:
-        key_block = ATTN_KEY_BLOCK if head_dim == 64 else ATTN_KEY_BLOCK_HD128
+        key_block = attn_key_block(head_dim)
     if key_block == 64:
         raise ValueError("rope_flash_attn_varlen_qkv: the 64-key dK/dV kernel has no rotary epilogue; use rope_ + flash_attn_varlen_qkv")
-    return _RopeFlashAttnVarlenQKV.apply(qkv, cos, sin, num_heads, num_kv_heads, cu, tiles, k_tiles, scale, key_block,
-                                         bool(fold_forward), fwd_tiles)[0]
+    return _FlashAttnVarlenQKV.apply(qkv, cos, sin, num_heads, num_kv_heads, cu, tiles, k_tiles, scale, key_block,
+                                     bool(fold_forward), fwd_tiles)[0]
 
 
 FWD_ONLY_CALLS = 0    # forward-only fused rotary + attention calls so far (tests read it: the inference surface ran the hand-written path)
@@ -1045,35 +1042,26 @@ def rope_flash_attn_varlen_qkv_fwd(qkv, cos, sin, num_heads, num_kv_heads, cu, t
     `rpo_rope` in place on the k heads of the fresh projection output, then the attention forward, which rotates the q block it
     loads anyway; no key-block table, no lse buffer.  Same kernels and same arithmetic as the training forward."""
     global FWD_ONLY_CALLS
-    if head_dim not in (64, 128):
-        raise ValueError("rope_flash_attn_varlen_qkv_fwd: head_dim must be 64 or 128")
-    if qkv.shape[-1] != (num_heads + 2 * num_kv_heads) * head_dim or not qkv.is_contiguous():
-        raise ValueError("rope_flash_attn_varlen_qkv_fwd: qkv must be a contiguous [..., T, (nh + 2 nkv) * head_dim] tensor")
+    _check_qkv("rope_flash_attn_varlen_qkv_fwd", qkv, num_heads, num_kv_heads, head_dim)
     if torch.is_grad_enabled() and qkv.requires_grad:
         raise RuntimeError("rope_flash_attn_varlen_qkv_fwd is forward-only; use rope_flash_attn_varlen_qkv under autograd")
     x = qkv.view(-1, qkv.shape[-1])
-    lib = _lib.load()
-    ptr = x.data_ptr() + num_heads * head_dim * x.element_size()
-    with torch.cuda.device(x.device):
-        check(lib.rpo_rope(ptr, ptr, x.shape[1], cos.data_ptr(), sin.data_ptr(), x.shape[0], num_kv_heads, head_dim, cos.shape[0],
-                           _dt(x), 0, _stream(x)), "rpo_rope")
-    q, k, v = _FlashAttnVarlenQKV._views(x, num_heads, num_kv_heads, head_dim)
+    _rope_heads_(x, cos, sin, num_heads, num_kv_heads, head_dim)
     FWD_ONLY_CALLS += 1
-    return flash_attn_varlen_fwd(q, k, v, cu, tiles if fwd_tiles is None else fwd_tiles, scale, rope=(cos, sin),
-                                 q_block=128 if fwd_tiles is None else 64, want_lse=False)[0]
+    work, q_block = _fwd_work(tiles, fwd_tiles)
+    return flash_attn_varlen_fwd(*_qkv_views(x, num_heads, num_kv_heads, head_dim), cu, work, scale, rope=(cos, sin),
+                                 q_block=q_block, want_lse=False)[0]
 
 
 def flash_attn_varlen_qkv(qkv, num_heads, num_kv_heads, cu, tiles, k_tiles, scale, key_block=None, head_dim: int = 64, fwd_tiles=None):
     """qkv: [T, (num_heads + 2 num_kv_heads) * head_dim] bf16, contiguous rows -> out [T, num_heads, head_dim]; head_dim 64
     or 128; key_block (None: the head_dim's default) = the block_n `k_tiles` was built with; fwd_tiles: the forward's own list
     (`attn_fwd_tile_table`) or None."""
-    if head_dim not in (64, 128):
-        raise ValueError("flash_attn_varlen_qkv: head_dim must be 64 or 128")
-    if qkv.dim() != 2 or qkv.shape[1] != (num_heads + 2 * num_kv_heads) * head_dim or not qkv.is_contiguous():
-        raise ValueError("flash_attn_varlen_qkv: qkv must be a contiguous [T, (nh + 2 nkv) * head_dim] tensor")
+    _check_qkv("flash_attn_varlen_qkv", qkv, num_heads, num_kv_heads, head_dim, flat=True)
     if key_block is None:
-        key_block = ATTN_KEY_BLOCK if head_dim == 64 else ATTN_KEY_BLOCK_HD128
-    return _FlashAttnVarlenQKV.apply(qkv, num_heads, num_kv_heads, cu, tiles, k_tiles, scale, key_block, fwd_tiles)
+        key_block = attn_key_block(head_dim)
+    return _FlashAttnVarlenQKV.apply(qkv, None, None, num_heads, num_kv_heads, cu, tiles, k_tiles, scale, key_block, False,
+                                     fwd_tiles)
 
 
 # ------------------------------------------------------------------------------------------------

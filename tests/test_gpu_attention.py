@@ -732,3 +732,158 @@ def test_default_build_refuses_the_optional_one_wave_64_kernels():
     with pytest.raises(RankPOHipError, match="status -2"):
         ops.flash_attn_varlen_bwd(q, k, v, out, torch.randn_like(out), lse, cu, t64, ops.attn_key_tile_table(lens, DEV, nkv), 0.125,
                                   q_block=64)
+
+
+FWD_ARGS = ("q", "k", "v", "q_stride", "k_stride", "v_stride", "cu", "tiles", "ntiles", "tile_cols", "total_tokens", "nh", "nkv", "hd",
+            "scale", "out", "out_stride", "lse", "lse_max_len", "rope_cos", "rope_sin", "rope_period", "q_block", "stream")
+BWD_ARGS = ("q", "k", "v", "out", "dout", "q_stride", "k_stride", "v_stride", "out_stride", "dout_stride", "cu", "q_tiles", "n_q_tiles",
+            "q_tile_cols", "k_tiles", "n_k_tiles", "key_block", "sweep_down", "total_tokens", "nh", "nkv", "hd", "scale", "lse", "delta",
+            "dq", "dk", "dv", "dq_stride", "dk_stride", "dv_stride", "rope_cos", "rope_sin", "rope_period", "q_block", "stream")
+INVALID, UNSUPPORTED = -1, -2
+
+
+@pytest.mark.parametrize("hd", [64, 128])
+def test_flash_attn_entries_refuse_what_they_refused(hd):
+    """Every refusal of rpo_flash_attn_fwd / rpo_flash_attn_bwd through the C calls themselves, one row per rule, and rows where two
+    faults coincide so that the ORDER of the rules shows (the entries interleave INVALID_ARG and UNSUPPORTED tests: the forward
+    answers the q_block rule before the rope-pair rule, the backward the rope rules before the list sizes).  Every refused call
+    returns before any launch; one valid call per entry runs at the end and gives what the ops give."""
+    from rankpo_amd import ops, _lib
+    lib = _lib.load()
+    default_build = not (lib.rpo_build_flags() & _lib.RPO_BUILD_ONEWAVE64)
+    torch.manual_seed(hd)
+    lens, nh, nkv = [1, 33], 4, 1
+    T, W = sum(lens), (nh + 2 * nkv) * hd
+    qkv = torch.randn(T, W, device=DEV).to(torch.bfloat16)
+    dqkv = torch.empty_like(qkv)
+    cu = torch.tensor([0] + list(np.cumsum(lens)), dtype=torch.int32, device=DEV)
+    tiles = ops.attn_tile_table(lens, DEV, nh, nkv)
+    t64 = ops.attn_fwd_tile_table(lens, DEV, nh, nkv, hd, force=True)         # 64 queries x 4 heads per entry
+    key_block = 256 if hd == 64 else 128
+    k_tiles = ops.attn_key_tile_table(lens, DEV, nkv, key_block)
+    assert tiles.shape[1] == 3 and tiles.shape[0] % 8 == 0 and t64 is not None
+    cos = torch.rand(64, hd // 2, device=DEV)
+    sin = torch.rand(64, hd // 2, device=DEV)
+    out = torch.empty(T, nh * hd, device=DEV, dtype=torch.bfloat16)
+    lse = torch.empty(nh, T, device=DEV)
+    dout = torch.randn(T, nh * hd, device=DEV).to(torch.bfloat16)
+    delta = torch.empty(2, nh, T, device=DEV)
+    st = torch.cuda.current_stream().cuda_stream
+    qp, kp, vp = qkv.data_ptr(), qkv.data_ptr() + nh * hd * 2, qkv.data_ptr() + (nh + nkv) * hd * 2
+    dqp, dkp, dvp = dqkv.data_ptr(), dqkv.data_ptr() + nh * hd * 2, dqkv.data_ptr() + (nh + nkv) * hd * 2
+    rope = dict(rope_cos=cos.data_ptr(), rope_sin=sin.data_ptr(), rope_period=64)
+    fwd_ok = dict(q=qp, k=kp, v=vp, q_stride=W, k_stride=W, v_stride=W, cu=cu.data_ptr(), tiles=tiles.data_ptr(),
+                  ntiles=tiles.shape[0], tile_cols=3, total_tokens=T, nh=nh, nkv=nkv, hd=hd, scale=0.125, out=out.data_ptr(),
+                  out_stride=nh * hd, lse=lse.data_ptr(), lse_max_len=0, rope_cos=None, rope_sin=None, rope_period=0, q_block=128,
+                  stream=st)
+    bwd_ok = dict(q=qp, k=kp, v=vp, out=out.data_ptr(), dout=dout.data_ptr(), q_stride=W, k_stride=W, v_stride=W, out_stride=nh * hd,
+                  dout_stride=nh * hd, cu=cu.data_ptr(), q_tiles=tiles.data_ptr(), n_q_tiles=tiles.shape[0], q_tile_cols=3,
+                  k_tiles=k_tiles.data_ptr(), n_k_tiles=k_tiles.shape[0], key_block=key_block, sweep_down=0, total_tokens=T, nh=nh,
+                  nkv=nkv, hd=hd, scale=0.125, lse=lse.data_ptr(), delta=delta.data_ptr(), dq=dqp, dk=dkp, dv=dvp, dq_stride=W,
+                  dk_stride=W, dv_stride=W, rope_cos=None, rope_sin=None, rope_period=0, q_block=128, stream=st)
+    one_wave = dict(q_block=64, tiles=t64.data_ptr(), ntiles=t64.shape[0])
+    one_wave_bwd = dict(q_block=64, q_tiles=t64.data_ptr(), n_q_tiles=t64.shape[0])
+    lone_cos, lone_sin = dict(rope, rope_sin=None), dict(rope, rope_cos=None)
+
+    fwd_rows = [(f"null {p}", {p: None}, INVALID) for p in ("q", "k", "v", "cu", "tiles", "out")] + [
+        ("ntiles 0", dict(ntiles=0), INVALID),
+        ("total_tokens 0", dict(total_tokens=0), INVALID),
+        ("q_block 32", dict(q_block=32), UNSUPPORTED),
+        ("q_block 64, group of 1", dict(one_wave, nkv=4), UNSUPPORTED),
+        ("q_block 64, group of 2", dict(one_wave, nkv=2), UNSUPPORTED),
+        ("cos without sin", lone_cos, INVALID),
+        ("sin without cos", lone_sin, INVALID),
+        ("rope with period 0", dict(rope, rope_period=0), INVALID),
+        ("misaligned cos", dict(rope, rope_cos=cos.data_ptr() + 4), UNSUPPORTED),
+        ("misaligned sin", dict(rope, rope_sin=sin.data_ptr() + 8), UNSUPPORTED),
+        ("tile_cols 4", dict(tile_cols=4), UNSUPPORTED),
+        ("tile_cols 3, ntiles % 8", dict(ntiles=tiles.shape[0] - 1), UNSUPPORTED),
+        ("head_dim 96", dict(hd=96), UNSUPPORTED),
+        ("heads % kv heads", dict(nkv=3), UNSUPPORTED),
+        ("no kv heads", dict(nkv=0), UNSUPPORTED),
+        ("65536 heads", dict(nh=65536), UNSUPPORTED),
+        ("q_stride % 8", dict(q_stride=W + 4), UNSUPPORTED),
+        ("k_stride % 8", dict(k_stride=W + 4), UNSUPPORTED),
+        ("misaligned q", dict(q=qp + 8), UNSUPPORTED),
+        ("misaligned v", dict(v=vp + 8), UNSUPPORTED),
+        ("out_stride % 4", dict(out_stride=nh * hd + 2), UNSUPPORTED),
+        ("out not 8-byte aligned", dict(out=out.data_ptr() + 4), UNSUPPORTED),
+        # two at once: the rule that stands first answers
+        ("null q + q_block 32", dict(q=None, q_block=32), INVALID),
+        ("q_block 32 + cos without sin", dict(lone_cos, q_block=32), UNSUPPORTED),
+        ("cos without sin + tile_cols 4", dict(lone_cos, tile_cols=4), INVALID),
+        ("rope with period 0 + head_dim 96", dict(rope, rope_period=0, hd=96), INVALID),
+        ("misaligned cos + total_tokens 0", dict(rope, rope_cos=cos.data_ptr() + 4, total_tokens=0), INVALID),
+    ]
+    if hd == 128:
+        fwd_rows += [("q_block 64, out_stride % 8", dict(one_wave, out_stride=nh * hd + 4), UNSUPPORTED),
+                     ("q_block 64, out not 16-byte aligned", dict(one_wave, out=out.data_ptr() + 8), UNSUPPORTED)]
+    elif default_build:
+        fwd_rows += [("q_block 64 at head_dim 64, default build", one_wave, UNSUPPORTED),
+                     ("the same + cos without sin", dict(one_wave, **lone_cos), INVALID)]
+
+    bwd_rows = [(f"null {p}", {p: None}, INVALID)
+                for p in ("q", "k", "v", "out", "dout", "cu", "q_tiles", "k_tiles", "lse", "delta", "dq", "dk", "dv")] + [
+        ("n_q_tiles 0", dict(n_q_tiles=0), INVALID),
+        ("n_k_tiles 0", dict(n_k_tiles=0), INVALID),
+        ("total_tokens 0", dict(total_tokens=0), INVALID),
+        ("q_block 32", dict(q_block=32), UNSUPPORTED),
+        ("q_block 64, group of 1", dict(one_wave_bwd, nkv=4), UNSUPPORTED),
+        ("q_block 64, dq_stride % 8", dict(one_wave_bwd, dq_stride=W + 4), UNSUPPORTED),
+        ("cos without sin", lone_cos, INVALID),
+        ("sin without cos", lone_sin, INVALID),
+        ("rope with period 0", dict(rope, rope_period=0), INVALID),
+        ("misaligned cos", dict(rope, rope_cos=cos.data_ptr() + 4), UNSUPPORTED),
+        ("misaligned sin", dict(rope, rope_sin=sin.data_ptr() + 8), UNSUPPORTED),
+        ("key_block 64 with rope", dict(rope, key_block=64), UNSUPPORTED),
+        ("q_tile_cols 4", dict(q_tile_cols=4), UNSUPPORTED),
+        ("q_tile_cols 3, n_q_tiles % 8", dict(n_q_tiles=tiles.shape[0] - 1), UNSUPPORTED),
+        ("head_dim 96", dict(hd=96, key_block=256), UNSUPPORTED),
+        ("heads % kv heads", dict(nkv=3), UNSUPPORTED),
+        ("no kv heads", dict(nkv=0), UNSUPPORTED),
+        ("65536 heads", dict(nh=65536), UNSUPPORTED),
+        ("q_stride % 8", dict(q_stride=W + 4), UNSUPPORTED),
+        ("misaligned q", dict(q=qp + 8), UNSUPPORTED),
+        ("out_stride % 8", dict(out_stride=nh * hd + 4), UNSUPPORTED),
+        ("dout not 16-byte aligned", dict(dout=dout.data_ptr() + 8), UNSUPPORTED),
+        ("dq_stride % 4", dict(dq_stride=W + 2), UNSUPPORTED),
+        ("dv_stride % 4", dict(dv_stride=W + 2), UNSUPPORTED),
+        ("key_block 128 at head_dim 64" if hd == 64 else "key_block 256 at head_dim 128", dict(key_block=384 - key_block), UNSUPPORTED),
+        ("key_block 32", dict(key_block=32), UNSUPPORTED),
+        # two at once
+        ("null dv + q_block 32", dict(dv=None, q_block=32), INVALID),
+        ("q_block 32 + cos without sin", dict(lone_cos, q_block=32), UNSUPPORTED),
+        ("cos without sin + key_block 32", dict(lone_cos, key_block=32), INVALID),
+        ("key_block 64 with rope + n_q_tiles 0", dict(rope, key_block=64, n_q_tiles=0), UNSUPPORTED),
+        ("misaligned cos + n_k_tiles 0", dict(rope, rope_cos=cos.data_ptr() + 4, n_k_tiles=0), UNSUPPORTED),
+        ("key_block 32 + total_tokens 0", dict(key_block=32, total_tokens=0), INVALID),
+        ("q_tile_cols 4 + n_q_tiles 0", dict(q_tile_cols=4, n_q_tiles=0), INVALID),
+        ("head_dim 96 + key_block 128", dict(hd=96, key_block=128), UNSUPPORTED),
+    ]
+    if hd == 128:
+        bwd_rows += [("q_block 64 at head_dim 128", one_wave_bwd, UNSUPPORTED),
+                     ("key_block 64 at head_dim 128", dict(key_block=64), UNSUPPORTED)]
+    elif default_build:
+        bwd_rows += [("q_block 64 at head_dim 64, default build", one_wave_bwd, UNSUPPORTED),
+                     ("the same + cos without sin", dict(one_wave_bwd, **lone_cos), UNSUPPORTED)]
+
+    for entry, names, ok, rows in ((lib.rpo_flash_attn_fwd, FWD_ARGS, fwd_ok, fwd_rows), (lib.rpo_flash_attn_bwd, BWD_ARGS, bwd_ok, bwd_rows)):
+        assert sorted(ok) == sorted(names)
+        for label, change, want in rows:
+            assert set(change) <= set(names), label
+            args = dict(ok, **change)
+            assert entry(*(args[n] for n in names)) == want, (entry.__name__, hd, label)
+    torch.cuda.synchronize()
+
+    # the valid calls: what the ops give on the same buffer
+    out.fill_(float("nan")); dqkv.fill_(float("nan"))
+    assert lib.rpo_flash_attn_fwd(*(fwd_ok[n] for n in FWD_ARGS)) == 0
+    assert lib.rpo_flash_attn_bwd(*(bwd_ok[n] for n in BWD_ARGS)) == 0
+    torch.cuda.synchronize()
+    q, k, v = (t.unflatten(1, (-1, hd)) for t in qkv.split([nh * hd, nkv * hd, nkv * hd], 1))
+    ro, rl = ops.flash_attn_varlen_fwd(q, k, v, cu, tiles, 0.125)
+    assert torch.equal(out.view(T, nh, hd), ro) and torch.equal(lse, rl)
+    rq, rk, rv = ops.flash_attn_varlen_bwd(q, k, v, ro, dout.view(T, nh, hd), rl, cu, tiles, k_tiles, 0.125, key_block=key_block,
+                                           sweep_down=False)
+    dq, dk, dv = dqkv.split([nh * hd, nkv * hd, nkv * hd], 1)
+    assert torch.equal(dq, rq.view(T, -1)) and torch.equal(dk, rk.view(T, -1)) and torch.equal(dv, rv.view(T, -1))
