@@ -1470,6 +1470,10 @@ __global__ __launch_bounds__(256) void infonce_first_bwd_kernel(
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
+#ifndef RPO_SIM_PERSIST
+#define RPO_SIM_PERSIST 1       // 0: one block per tile (rounds 1-4), the A/B arm of profiles/r05_sim_tile256_persistent_ab.txt
+#endif
+
 enum FwdPath { PATH_TILE = 0, PATH_SKINNY = 1, PATH_ROWWISE = 2, PATH_TILE256 = 3 };
 
 struct Plan {
@@ -1532,6 +1536,27 @@ static Plan make_plan(int64_t Q, int64_t P, int64_t d, int dtype, bool aligned) 
     return pl;
 }
 
+// The one launch of the 256 x 256 frame, whatever the epilogue: q [Q, d] with row stride ldq against p [P, d] with row stride ldp
+// (elements; PLANES: the rows are 3 d wide), `out` with row stride ldc as EPI writes it (0 / 1: bf16 scores, 4: f32 scores, 2 / 3:
+// none -- the survivors go to `flt`).  Persistent grid of one block per CU; RPO_SIM_PERSIST=0 gives EPI 0 / 1 a block per tile.
+template <int EPI, bool F16 = false, bool PLANES = false>
+int launch_tile256(const void* q, int64_t ldq, const void* p, int64_t ldp, int64_t Q, int64_t P, int64_t d, void* out, int64_t ldc,
+                   hipStream_t st, const SimFilter& flt = SimFilter{}, float temperature = 1.0f, int scale = 0, int do_stats = 0,
+                   float2* partial = nullptr) {
+    const int64_t nPt = rpo_cdiv(P, kBigTile), nQt = rpo_cdiv(Q, kBigTile), ntile = nPt * nQt;
+    if (ntile > 0x7fffffff) return RPO_ERR_UNSUPPORTED;
+    // once per instantiation (the initialiser of a local static runs once)
+    static const hipError_t attr = hipFuncSetAttribute((const void*)sim_tile256_kernel<EPI, F16, PLANES>,
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, kBigLdsBytes);
+    (void)attr;
+    const bool persist = EPI >= 2 || RPO_SIM_PERSIST;
+    // the kernel names the strides after its MFMA operands: `lda` is the row stride of p, `ldb` that of q.  Mapped here and nowhere else
+    RPO_LAUNCH((sim_tile256_kernel<EPI, F16, PLANES>), dim3((unsigned)(persist ? std::min<int64_t>(ntile, kBigPersistBlocks) : ntile)),
+               dim3(kBigThreads), kBigLdsBytes, st, (const bf16_t*)q, (const bf16_t*)p, Q, P, d, /*lda=*/ldp, /*ldb=*/ldq, ldc,
+               temperature, scale, do_stats, (bf16_t*)out, partial, (int)nPt, (int)nQt, /*stagger=*/1, /*dbg=*/0, flt);
+    return rpo_launch_status();
+}
+
 template <typename T>
 int fwd_impl(const void* q, const void* p, int64_t Q, int64_t P, int64_t d, float temperature, int target_mode,
              void* scores_out, float* lse_out, float* loss_out, void* ws, size_t ws_bytes, hipStream_t st) {
@@ -1556,41 +1581,25 @@ int fwd_impl(const void* q, const void* p, int64_t Q, int64_t P, int64_t d, floa
     float2* partial = do_stats ? (float2*)(wsb + pl.off_partial) : nullptr;
     bool fused_finalize = false;      // the forward kernel wrote lse and loss itself (single-block skinny launch)
     if (pl.path == PATH_TILE) {
-        static bool attr_set = false;   // idempotent; a race only repeats the same call
-        if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)sim_tile_kernel<T, 128, 128, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      tile_lds_bytes(128, 128, 2));
-            (void)hipFuncSetAttribute((const void*)sim_tile_kernel<T, 128, 64, 3>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      tile_lds_bytes(128, 64, 3));
-            (void)hipFuncSetAttribute((const void*)sim_tile_kernel<T, 64, 64, 8>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      tile_lds_bytes(64, 64, 8));
-            attr_set = true;
-        }
         const dim3 grid((unsigned)(pl.nPt * pl.nQt)), block(kTileThreads);
-        if (pl.tp == 128 && pl.tq == 128)
-            RPO_LAUNCH((sim_tile_kernel<T, 128, 128, 2>), grid, block, tile_lds_bytes(128, 128, 2), st, (const T*)q, (const T*)p, Q, P,
-                       d, temperature, scale, do_stats ? 1 : 0, (T*)scores_out, partial, pl.nPt, pl.nQt);
-        else if (pl.tp == 128)
-            RPO_LAUNCH((sim_tile_kernel<T, 128, 64, 3>), grid, block, tile_lds_bytes(128, 64, 3), st, (const T*)q, (const T*)p, Q, P,
-                       d, temperature, scale, do_stats ? 1 : 0, (T*)scores_out, partial, pl.nPt, pl.nQt);
-        else
-            RPO_LAUNCH((sim_tile_kernel<T, 64, 64, 8>), grid, block, tile_lds_bytes(64, 64, 8), st, (const T*)q, (const T*)p, Q, P, d,
-                       temperature, scale, do_stats ? 1 : 0, (T*)scores_out, partial, pl.nPt, pl.nQt);
+        // sim_tile_kernel<T, TP, TQ, STAGES>: its LDS attribute once per instance (a local static's initialiser), one argument list
+#define RPO_TILE_LAUNCH(...)                                                                                                    \
+    do {                                                                                                                        \
+        static const hipError_t attr = hipFuncSetAttribute((const void*)sim_tile_kernel<T, __VA_ARGS__>,                        \
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, tile_lds_bytes(__VA_ARGS__)); \
+        (void)attr;                                                                                                             \
+        RPO_LAUNCH((sim_tile_kernel<T, __VA_ARGS__>), grid, block, tile_lds_bytes(__VA_ARGS__), st, (const T*)q, (const T*)p, Q, P, d, \
+                   temperature, scale, do_stats ? 1 : 0, (T*)scores_out, partial, pl.nPt, pl.nQt);                              \
+    } while (0)
+        if (pl.tp == 128 && pl.tq == 128) RPO_TILE_LAUNCH(128, 128, 2);
+        else if (pl.tp == 128) RPO_TILE_LAUNCH(128, 64, 3);
+        else RPO_TILE_LAUNCH(64, 64, 8);
+#undef RPO_TILE_LAUNCH
     } else if (pl.path == PATH_TILE256) {
         if constexpr (__is_same(T, bf16_t)) {          // make_plan picks this path for bf16 only
-            static bool attr_set256 = false;
-            if (!attr_set256) {
-                (void)hipFuncSetAttribute((const void*)sim_tile256_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          kBigLdsBytes);
-                attr_set256 = true;
-            }
-#ifndef RPO_SIM_PERSIST
-#define RPO_SIM_PERSIST 1       // 0: one block per tile (rounds 1-4), the A/B arm of profiles/r05_sim_tile256_persistent_ab.txt
-#endif
-            const int64_t ntile = (int64_t)pl.nPt * pl.nQt;
-            RPO_LAUNCH(sim_tile256_kernel<0>, dim3((unsigned)(RPO_SIM_PERSIST ? std::min<int64_t>(ntile, kBigPersistBlocks) : ntile)),
-                       dim3(kBigThreads), kBigLdsBytes, st, (const bf16_t*)q, (const bf16_t*)p, Q, P, d, d, d, P, temperature, scale,
-                       do_stats ? 1 : 0, (bf16_t*)scores_out, partial, pl.nPt, pl.nQt, /*stagger=*/1, /*dbg=*/0, SimFilter{});
+            const int rc256 = launch_tile256<0>(q, d, p, d, Q, P, d, scores_out, P, st, SimFilter{}, temperature, scale, do_stats ? 1 : 0,
+                                                partial);
+            if (rc256 != RPO_OK) return rc256;
         }
     } else if (pl.path == PATH_SKINNY) {
         const int ng = Q <= 16 ? 4 : 1;
@@ -1604,12 +1613,9 @@ int fwd_impl(const void* q, const void* p, int64_t Q, int64_t P, int64_t d, floa
             const int64_t lds = stage > accb ? stage : accb;
             if (Q <= 16 && pl.nPb <= kSmallMaxGroups && kcb <= 8192 && Q * (kcb / 1024) <= 8 * kSmallQPieces &&
                 P * (kcb / 1024) <= 8 * kSmallPPieces && lds <= 150 * 1024 && row_bytes % 16 == 0) {
-                static bool attr_set_small = false;
-                if (!attr_set_small) {
-                    (void)hipFuncSetAttribute((const void*)sim_small_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                              150 * 1024);
-                    attr_set_small = true;
-                }
+                static const hipError_t attr = hipFuncSetAttribute((const void*)sim_small_kernel<T>,
+                                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+                (void)attr;
                 RPO_LAUNCH(sim_small_kernel<T>, dim3(1), dim3(kSmallThreads), (size_t)lds, st, (const T*)q, (const T*)p, Q, P, d,
                            temperature, scale, do_stats ? 1 : 0, P / Q, (T*)scores_out, lse_out, loss_out, (int)kcb, (int)lds);
                 return rpo_launch_status();
@@ -1631,12 +1637,12 @@ int fwd_impl(const void* q, const void* p, int64_t Q, int64_t P, int64_t d, floa
         }
         fused_finalize = do_stats && (nblk == 1 || slot >= 0);
         const dim3 grid(nblk), block(kSkinnyThreads);
-        if (ng == 4)
-            RPO_LAUNCH((sim_skinny_kernel<T, 4>), grid, block, 0, st, (const T*)q, (const T*)p, Q, P, d, temperature, scale,
-                       do_stats ? 1 : 0, P / Q, (T*)scores_out, partial, lse_out, loss_out, slot, epoch);
-        else
-            RPO_LAUNCH((sim_skinny_kernel<T, 1>), grid, block, 0, st, (const T*)q, (const T*)p, Q, P, d, temperature, scale,
-                       do_stats ? 1 : 0, P / Q, (T*)scores_out, partial, lse_out, loss_out, slot, epoch);
+#define RPO_SKINNY_LAUNCH(NG)                                                                                             \
+    RPO_LAUNCH((sim_skinny_kernel<T, NG>), grid, block, 0, st, (const T*)q, (const T*)p, Q, P, d, temperature, scale,    \
+               do_stats ? 1 : 0, P / Q, (T*)scores_out, partial, lse_out, loss_out, slot, epoch)
+        if (ng == 4) RPO_SKINNY_LAUNCH(4);
+        else RPO_SKINNY_LAUNCH(1);
+#undef RPO_SKINNY_LAUNCH
     } else {
         RPO_LAUNCH(sim_rowwise_kernel<T>, dim3((unsigned)Q), dim3(256), 0, st, (const T*)q, (const T*)p, Q,
                            P, d, temperature, scale, do_stats ? 1 : 0, (T*)scores_out, partial);
@@ -1683,6 +1689,14 @@ int bwd_impl(const void* q, const void* p, const void* scores, const float* lse,
     return rpo_launch_status();
 }
 
+// f(T{}) with T the storage type of a dtype the caller has checked (rpo_dtype_ok).  Not bert_ops.hip's dtype_dispatch: that one walks
+// bf16, fp16, f32, and the order of the arms is the order in which hipcc emits the kernels' instances into this unit's code object
+template <typename F> int by_dtype(int dtype, F f) {
+    if (dtype == RPO_DT_F32) return f(float{});
+    if (dtype == RPO_DT_F16) return f(f16_t{});
+    return f(bf16_t{});
+}
+
 static int check_common(const void* q, const void* p, int64_t Q, int64_t P, int64_t d, int dtype, float temperature,
                         int target_mode) {
     if (!q || !p || Q <= 0 || P <= 0 || d <= 0) return RPO_ERR_INVALID_ARG;
@@ -1725,15 +1739,10 @@ extern "C" int rpo_infonce_fwd(const void* q, const void* p, int64_t Q, int64_t 
     if (!scores_out) return RPO_ERR_INVALID_ARG;
     if ((lse_out == nullptr) != (loss_out == nullptr)) return RPO_ERR_INVALID_ARG;
     if (lse_out && P < Q) return RPO_ERR_INVALID_ARG;   // target_i = i * (P // Q) needs group_size >= 1
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == RPO_DT_F32)
-        return fwd_impl<float>(q, p, Q, P, d, temperature, target_mode, scores_out, lse_out, loss_out, workspace,
-                               workspace_bytes, st);
-    if (dtype == RPO_DT_F16)
-        return fwd_impl<f16_t>(q, p, Q, P, d, temperature, target_mode, scores_out, lse_out, loss_out, workspace,
-                               workspace_bytes, st);
-    return fwd_impl<bf16_t>(q, p, Q, P, d, temperature, target_mode, scores_out, lse_out, loss_out, workspace,
-                            workspace_bytes, st);
+    return by_dtype(dtype, [&](auto t) {
+        return fwd_impl<decltype(t)>(q, p, Q, P, d, temperature, target_mode, scores_out, lse_out, loss_out, workspace, workspace_bytes,
+                                     (hipStream_t)stream);
+    });
 }
 
 extern "C" int rpo_infonce_bwd(const void* q, const void* p, const void* scores, const float* lse,
@@ -1752,15 +1761,10 @@ extern "C" int rpo_infonce_bwd(const void* q, const void* p, const void* scores,
     if (dq_out && q_rows == 0) dq_out = nullptr;
     if (dp_out && p_rows == 0) dp_out = nullptr;
     if (!dq_out && !dp_out) return RPO_OK;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == RPO_DT_F32)
-        return bwd_impl<float>(q, p, scores, lse, grad_loss, Q, P, d, temperature, target_mode, q_row0, q_rows,
-                               p_row0, p_rows, dq_out, dp_out, st);
-    if (dtype == RPO_DT_F16)
-        return bwd_impl<f16_t>(q, p, scores, lse, grad_loss, Q, P, d, temperature, target_mode, q_row0, q_rows,
-                               p_row0, p_rows, dq_out, dp_out, st);
-    return bwd_impl<bf16_t>(q, p, scores, lse, grad_loss, Q, P, d, temperature, target_mode, q_row0, q_rows, p_row0,
-                            p_rows, dq_out, dp_out, st);
+    return by_dtype(dtype, [&](auto t) {
+        return bwd_impl<decltype(t)>(q, p, scores, lse, grad_loss, Q, P, d, temperature, target_mode, q_row0, q_rows, p_row0, p_rows,
+                                     dq_out, dp_out, (hipStream_t)stream);
+    });
 }
 
 extern "C" int rpo_infonce_ds(const void* scores, const float* lse, const float* grad_loss, int64_t Q, int64_t P,
@@ -1774,42 +1778,43 @@ extern "C" int rpo_infonce_ds(const void* scores, const float* lse, const float*
     if (p_rows == 0) dst_out = nullptr;
     if (!ds_out && !dst_out) return RPO_OK;
     if (rpo_cdiv(Q, 64) > 65535) return RPO_ERR_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)rpo_cdiv(P, 64), (unsigned)rpo_cdiv(Q, 64));
-    if (dtype == RPO_DT_F32)
-        RPO_LAUNCH(infonce_ds_kernel<float>, grid, dim3(256), 0, st, (const float*)scores, lse, grad_loss, Q, P,
-                   temperature, P / Q, q_row0, q_rows, p_row0, p_rows, (float*)ds_out, (float*)dst_out);
-    else if (dtype == RPO_DT_F16)
-        RPO_LAUNCH(infonce_ds_kernel<f16_t>, grid, dim3(256), 0, st, (const f16_t*)scores, lse, grad_loss, Q, P,
-                   temperature, P / Q, q_row0, q_rows, p_row0, p_rows, (f16_t*)ds_out, (f16_t*)dst_out);
-    else
-        RPO_LAUNCH(infonce_ds_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)scores, lse, grad_loss, Q, P,
-                   temperature, P / Q, q_row0, q_rows, p_row0, p_rows, (bf16_t*)ds_out, (bf16_t*)dst_out);
-    return rpo_launch_status();
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        RPO_LAUNCH(infonce_ds_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, (const T*)scores, lse, grad_loss, Q, P, temperature,
+                   P / Q, q_row0, q_rows, p_row0, p_rows, (T*)ds_out, (T*)dst_out);
+        return rpo_launch_status();
+    });
 }
+
+// ---- the entries of the 256 x 256 frame.  What their argument checks share; each entry asks them at its own place, which decides
+// whether two coinciding faults answer RPO_ERR_INVALID_ARG or RPO_ERR_UNSUPPORTED (tests/test_gpu_kernels.py pins the rows)
+namespace {
+// both operands are there and the problem is not empty
+bool sim_operands_given(const void* q, const void* p, int64_t Q, int64_t P, int64_t d) { return q && p && Q > 0 && P > 0 && d > 0; }
+bool sim_dtype_16bit(int dtype) { return dtype == RPO_DT_BF16 || dtype == RPO_DT_F16; }
+// 16-byte LDS-DMA pieces of both operands, and a shape the frame scores (rpo_sim_topk_filter_ok / rpo_sim_planes_ok)
+bool sim_frame_takes(const void* q, const void* p, int shape_ok) { return rpo_aligned16(q) && rpo_aligned16(p) && shape_ok; }
+// the winners and candidate lists of a filter step -> *flt; false: a pointer is missing or a count is not positive
+bool sim_filter_args(const float* best_val, const int64_t* best_idx, float* cand_val, int64_t* cand_idx, int32_t* cand_cnt,
+                     int64_t col0, int k, int cap, SimFilter* flt) {
+    *flt = SimFilter{best_val, (const long long*)best_idx, cand_val, (long long*)cand_idx, cand_cnt, col0, k, cap};
+    return best_val && best_idx && cand_val && cand_idx && cand_cnt && col0 >= 0 && k > 0 && cap > 0;
+}
+}  // namespace
 
 // C [rows_b, rows_a] = B [rows_b, K] A [rows_a, K]^T (bf16 in, f32 accumulate, one rounding to bf16): see sim_tile256_kernel<1>.
 extern "C" int rpo_sim_gemm_nt(const void* a, int64_t rows_a, int64_t lda, const void* b, int64_t rows_b, int64_t ldb, int64_t K,
                                void* c, int64_t ldc, rpo_stream_t stream) {
-    if (!a || !b || !c || rows_a <= 0 || rows_b <= 0 || K <= 0) return RPO_ERR_INVALID_ARG;
+    if (!sim_operands_given(b, a, rows_b, rows_a, K) || !c) return RPO_ERR_INVALID_ARG;
     // the frame's K-step is 64 elements and its operands travel as 16-byte LDS-DMA pieces; the epilogue streams 256-byte row
     // segments out of LDS (the `staged` path of the forward): everything else is left to the caller's library GEMM
     if (K % 64 != 0 || lda % 8 != 0 || ldb % 8 != 0 || ldc % 8 != 0 || lda < K || ldb < K || ldc < rows_a || !rpo_aligned16(a) ||
         !rpo_aligned16(b) || !rpo_aligned16(c))
         return RPO_ERR_UNSUPPORTED;
-    const int64_t nPt = rpo_cdiv(rows_a, kBigTile), nQt = rpo_cdiv(rows_b, kBigTile);
-    if (nPt * nQt > 0x7fffffff) return RPO_ERR_UNSUPPORTED;
     // the kernel addresses its LDS-DMA pieces by 32-bit byte offsets from the operand bases
     if (rows_a * lda * 2 >= ((int64_t)1 << 32) || rows_b * ldb * 2 >= ((int64_t)1 << 32)) return RPO_ERR_UNSUPPORTED;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)sim_tile256_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, kBigLdsBytes);
-        attr_set = true;
-    }
-    RPO_LAUNCH(sim_tile256_kernel<1>, dim3((unsigned)(RPO_SIM_PERSIST ? std::min<int64_t>(nPt * nQt, kBigPersistBlocks) : nPt * nQt)),
-               dim3(kBigThreads), kBigLdsBytes, (hipStream_t)stream, (const bf16_t*)b, (const bf16_t*)a, rows_b, rows_a, K, lda, ldb, ldc,
-               1.0f, 0, 0, (bf16_t*)c, (float2*)nullptr, (int)nPt, (int)nQt, /*stagger=*/1, /*dbg=*/0, SimFilter{});
-    return rpo_launch_status();
+    return launch_tile256<1>(/*q=*/b, ldb, /*p=*/a, lda, rows_b, rows_a, K, c, ldc, (hipStream_t)stream);
 }
 
 // One step of the exact search (retrieval.FlatIPIndex.search; the k-selection of faiss.IndexFlatIP.search, reference
@@ -1825,58 +1830,26 @@ extern "C" int rpo_sim_topk_filter_ok(int64_t Q, int64_t P, int64_t d) {
 extern "C" int rpo_sim_topk_filter(const void* q, const void* p, int64_t Q, int64_t P, int64_t d, int dtype, int64_t col0, int k,
                                    int round_scores, const float* best_val, const int64_t* best_idx, float* cand_val,
                                    int64_t* cand_idx, int32_t* cand_cnt, int cap, rpo_stream_t stream) {
-    if (!q || !p || !best_val || !best_idx || !cand_val || !cand_idx || !cand_cnt || Q <= 0 || P <= 0 || d <= 0 || col0 < 0 ||
-        k <= 0 || cap <= 0 || (dtype != RPO_DT_BF16 && dtype != RPO_DT_F16))
+    SimFilter flt;
+    if (!sim_operands_given(q, p, Q, P, d) || !sim_filter_args(best_val, best_idx, cand_val, cand_idx, cand_cnt, col0, k, cap, &flt) ||
+        !sim_dtype_16bit(dtype))
         return RPO_ERR_INVALID_ARG;
     if (dtype == RPO_DT_F16 && round_scores) return RPO_ERR_UNSUPPORTED;        // fp16 operands: f32 scores only
-    if (!rpo_aligned16(q) || !rpo_aligned16(p) || !rpo_sim_topk_filter_ok(Q, P, d)) return RPO_ERR_UNSUPPORTED;
-    const int64_t nPt = rpo_cdiv(P, kBigTile), nQt = rpo_cdiv(Q, kBigTile);
-    if (nPt * nQt > 0x7fffffff) return RPO_ERR_UNSUPPORTED;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)sim_tile256_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, kBigLdsBytes);
-        (void)hipFuncSetAttribute((const void*)sim_tile256_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, kBigLdsBytes);
-        (void)hipFuncSetAttribute((const void*)sim_tile256_kernel<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kBigLdsBytes);
-        attr_set = true;
-    }
-    SimFilter flt{best_val, (const long long*)best_idx, cand_val, (long long*)cand_idx, cand_cnt, col0, k, cap};
-    const dim3 grid((unsigned)std::min<int64_t>(nPt * nQt, kBigPersistBlocks));
-#define RPO_FILTER_LAUNCH(...)                                                                                                   \
-    RPO_LAUNCH((sim_tile256_kernel<__VA_ARGS__>), grid, dim3(kBigThreads), kBigLdsBytes, (hipStream_t)stream, (const bf16_t*)q, \
-               (const bf16_t*)p, Q, P, d, d, d, P, 1.0f, 0, 0, (bf16_t*)nullptr, (float2*)nullptr, (int)nPt, (int)nQt,          \
-               /*stagger=*/1, /*dbg=*/0, flt)
-    if (dtype == RPO_DT_F16) RPO_FILTER_LAUNCH(3, true);
-    else if (round_scores) RPO_FILTER_LAUNCH(2);
-    else RPO_FILTER_LAUNCH(3);
-#undef RPO_FILTER_LAUNCH
-    return rpo_launch_status();
+    if (!sim_frame_takes(q, p, rpo_sim_topk_filter_ok(Q, P, d))) return RPO_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    if (round_scores) return launch_tile256<2>(q, d, p, d, Q, P, d, nullptr, P, st, flt);
+    if (dtype == RPO_DT_BF16) return launch_tile256<3>(q, d, p, d, Q, P, d, nullptr, P, st, flt);
+    return launch_tile256<3, true>(q, d, p, d, Q, P, d, nullptr, P, st, flt);
 }
 
 // scores f32 [Q, P] (row stride ldc) = q [Q, d] p [P, d]^T, bf16 or fp16 operands, f32 sums UNROUNDED, in the 256 x 256 frame's
 // summation order (sim_tile256_kernel<4>): the score matrix that goes with rpo_sim_topk_filter(round_scores = 0); same shapes.
 extern "C" int rpo_sim_scores_f32(const void* q, const void* p, int64_t Q, int64_t P, int64_t d, int dtype, float* scores, int64_t ldc,
                                   rpo_stream_t stream) {
-    if (!q || !p || !scores || Q <= 0 || P <= 0 || d <= 0 || ldc < P || (dtype != RPO_DT_BF16 && dtype != RPO_DT_F16))
-        return RPO_ERR_INVALID_ARG;
-    if (!rpo_aligned16(q) || !rpo_aligned16(p) || !rpo_sim_topk_filter_ok(Q, P, d)) return RPO_ERR_UNSUPPORTED;
-    const int64_t nPt = rpo_cdiv(P, kBigTile), nQt = rpo_cdiv(Q, kBigTile);
-    if (nPt * nQt > 0x7fffffff) return RPO_ERR_UNSUPPORTED;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)sim_tile256_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, kBigLdsBytes);
-        (void)hipFuncSetAttribute((const void*)sim_tile256_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kBigLdsBytes);
-        attr_set = true;
-    }
-    const dim3 grid((unsigned)std::min<int64_t>(nPt * nQt, kBigPersistBlocks));
-    if (dtype == RPO_DT_F16)
-        RPO_LAUNCH((sim_tile256_kernel<4, true>), grid, dim3(kBigThreads), kBigLdsBytes, (hipStream_t)stream, (const bf16_t*)q,
-                   (const bf16_t*)p, Q, P, d, d, d, ldc, 1.0f, 0, 0, (bf16_t*)scores, (float2*)nullptr, (int)nPt, (int)nQt,
-                   /*stagger=*/1, /*dbg=*/0, SimFilter{});
-    else
-        RPO_LAUNCH((sim_tile256_kernel<4>), grid, dim3(kBigThreads), kBigLdsBytes, (hipStream_t)stream, (const bf16_t*)q,
-                   (const bf16_t*)p, Q, P, d, d, d, ldc, 1.0f, 0, 0, (bf16_t*)scores, (float2*)nullptr, (int)nPt, (int)nQt,
-                   /*stagger=*/1, /*dbg=*/0, SimFilter{});
-    return rpo_launch_status();
+    if (!sim_operands_given(q, p, Q, P, d) || !scores || ldc < P || !sim_dtype_16bit(dtype)) return RPO_ERR_INVALID_ARG;
+    if (!sim_frame_takes(q, p, rpo_sim_topk_filter_ok(Q, P, d))) return RPO_ERR_UNSUPPORTED;
+    if (dtype == RPO_DT_BF16) return launch_tile256<4>(q, d, p, d, Q, P, d, scores, ldc, (hipStream_t)stream);
+    return launch_tile256<4, true>(q, d, p, d, Q, P, d, scores, ldc, (hipStream_t)stream);
 }
 
 // ---- the same two calls on bf16 PLANES of f32 operands (sim_tile256_kernel<3 / 4, false, true>): q [Q, 3 d], p [P, 3 d] as
@@ -1890,41 +1863,18 @@ extern "C" int rpo_sim_planes_ok(int64_t Q, int64_t P, int64_t d) {
 extern "C" int rpo_sim_topk_filter_planes(const void* q, const void* p, int64_t Q, int64_t P, int64_t d, int64_t col0, int k,
                                           const float* best_val, const int64_t* best_idx, float* cand_val, int64_t* cand_idx,
                                           int32_t* cand_cnt, int cap, rpo_stream_t stream) {
-    if (!q || !p || !best_val || !best_idx || !cand_val || !cand_idx || !cand_cnt || Q <= 0 || P <= 0 || d <= 0 || col0 < 0 ||
-        k <= 0 || cap <= 0)
+    SimFilter flt;
+    if (!sim_operands_given(q, p, Q, P, d) || !sim_filter_args(best_val, best_idx, cand_val, cand_idx, cand_cnt, col0, k, cap, &flt))
         return RPO_ERR_INVALID_ARG;
-    if (!rpo_aligned16(q) || !rpo_aligned16(p) || !rpo_sim_planes_ok(Q, P, d)) return RPO_ERR_UNSUPPORTED;
-    const int64_t nPt = rpo_cdiv(P, kBigTile), nQt = rpo_cdiv(Q, kBigTile);
-    if (nPt * nQt > 0x7fffffff) return RPO_ERR_UNSUPPORTED;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)sim_tile256_kernel<3, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kBigLdsBytes);
-        attr_set = true;
-    }
-    SimFilter flt{best_val, (const long long*)best_idx, cand_val, (long long*)cand_idx, cand_cnt, col0, k, cap};
-    const dim3 grid((unsigned)std::min<int64_t>(nPt * nQt, kBigPersistBlocks));
-    RPO_LAUNCH((sim_tile256_kernel<3, false, true>), grid, dim3(kBigThreads), kBigLdsBytes, (hipStream_t)stream, (const bf16_t*)q,
-               (const bf16_t*)p, Q, P, d, 3 * d, 3 * d, P, 1.0f, 0, 0, (bf16_t*)nullptr, (float2*)nullptr, (int)nPt, (int)nQt,
-               /*stagger=*/1, /*dbg=*/0, flt);
-    return rpo_launch_status();
+    if (!sim_frame_takes(q, p, rpo_sim_planes_ok(Q, P, d))) return RPO_ERR_UNSUPPORTED;
+    return launch_tile256<3, false, true>(q, 3 * d, p, 3 * d, Q, P, d, nullptr, P, (hipStream_t)stream, flt);
 }
 
 extern "C" int rpo_sim_scores_f32_planes(const void* q, const void* p, int64_t Q, int64_t P, int64_t d, float* scores, int64_t ldc,
                                          rpo_stream_t stream) {
-    if (!q || !p || !scores || Q <= 0 || P <= 0 || d <= 0 || ldc < P) return RPO_ERR_INVALID_ARG;
-    if (!rpo_aligned16(q) || !rpo_aligned16(p) || !rpo_sim_planes_ok(Q, P, d)) return RPO_ERR_UNSUPPORTED;
-    const int64_t nPt = rpo_cdiv(P, kBigTile), nQt = rpo_cdiv(Q, kBigTile);
-    if (nPt * nQt > 0x7fffffff) return RPO_ERR_UNSUPPORTED;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)sim_tile256_kernel<4, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kBigLdsBytes);
-        attr_set = true;
-    }
-    const dim3 grid((unsigned)std::min<int64_t>(nPt * nQt, kBigPersistBlocks));
-    RPO_LAUNCH((sim_tile256_kernel<4, false, true>), grid, dim3(kBigThreads), kBigLdsBytes, (hipStream_t)stream, (const bf16_t*)q,
-               (const bf16_t*)p, Q, P, d, 3 * d, 3 * d, ldc, 1.0f, 0, 0, (bf16_t*)scores, (float2*)nullptr, (int)nPt, (int)nQt,
-               /*stagger=*/1, /*dbg=*/0, SimFilter{});
-    return rpo_launch_status();
+    if (!sim_operands_given(q, p, Q, P, d) || !scores || ldc < P) return RPO_ERR_INVALID_ARG;
+    if (!sim_frame_takes(q, p, rpo_sim_planes_ok(Q, P, d))) return RPO_ERR_UNSUPPORTED;
+    return launch_tile256<4, false, true>(q, 3 * d, p, 3 * d, Q, P, d, scores, ldc, (hipStream_t)stream);
 }
 
 thread_local int rpo_tls_last_hip_error = 0;

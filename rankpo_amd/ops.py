@@ -1908,6 +1908,12 @@ def gelu(u):
 TOPK_MAX_K = 1024
 
 
+def _winners_ok(best_val, best_idx, lists: int, k: int) -> bool:
+    """best_val / best_idx are contiguous f32 / int64 [lists, k]."""
+    return best_val.shape == (lists, k) and best_idx.shape == (lists, k) and best_val.is_contiguous() and best_idx.is_contiguous() \
+        and best_val.dtype == torch.float32 and best_idx.dtype == torch.int64
+
+
 def topk_merge(scores, col0: int, best_val=None, best_idx=None, k: int = 100, split: int = 1):
     """Merges the top-k of `scores` ([rows, cols] f32 / bf16 / fp16, the chunk of corpus rows [col0, col0 + cols)) into the winners
     so far (`best_val` f32 [rows * split, k], `best_idx` int64 [rows * split, k]; None: start).  Order: value descending, ties by
@@ -1927,8 +1933,7 @@ def topk_merge(scores, col0: int, best_val=None, best_idx=None, k: int = 100, sp
     if first:
         best_val = torch.empty((rows * split, k), dtype=torch.float32, device=scores.device)
         best_idx = torch.empty((rows * split, k), dtype=torch.int64, device=scores.device)
-    elif best_val.shape != (rows * split, k) or best_idx.shape != (rows * split, k) or not best_val.is_contiguous() \
-            or not best_idx.is_contiguous() or best_val.dtype != torch.float32 or best_idx.dtype != torch.int64:
+    elif not _winners_ok(best_val, best_idx, rows * split, k):
         raise ValueError("topk_merge: best_val / best_idx must be contiguous f32 / int64 [rows * split, k]")
     with torch.cuda.device(scores.device):
         check(lib.rpo_topk_merge_split(scores.data_ptr(), scores.stride(0), rows, cols, int(col0), k, _dt(scores), int(split),
@@ -1966,14 +1971,20 @@ def search_filter_ok(nq: int, rows: int, d: int) -> bool:
     return bool(_lib.load().rpo_sim_topk_filter_ok(int(nq), int(rows), int(d)))
 
 
+def _frame_takes(q, p, dtypes, cols_per_d: int, shape_ok) -> bool:
+    """Operands of the 256 x 256 frame: two contiguous, 16-byte aligned [rows, cols_per_d * d] matrices of one of `dtypes`, and a
+    problem the C shape predicate `shape_ok(Q, P, d)` admits."""
+    if not (q.dtype in dtypes and p.dtype == q.dtype and q.dim() == 2 and p.dim() == 2 and q.is_contiguous() and p.is_contiguous()
+            and q.shape[1] == p.shape[1] and q.shape[1] % cols_per_d == 0 and q.data_ptr() % 16 == 0 and p.data_ptr() % 16 == 0):
+        return False
+    return bool(shape_ok(q.shape[0], p.shape[0], q.shape[1] // cols_per_d))
+
+
 def search_filter_takes(q, p) -> bool:
     """Shapes rpo_sim_topk_filter takes: bf16 (or, with f32 scores, fp16) rows, 16-byte aligned, and a problem `similarity` scores
     with the same 256 x 256 kernel (rpo_sim_topk_filter_ok: > 64 query rows, d % 64 == 0, >= 192 tiles, operands below 4 GB) -- so
     the fused step changes no bit."""
-    if not (q.dtype in (torch.bfloat16, torch.float16) and p.dtype == q.dtype and q.dim() == 2 and p.dim() == 2 and q.is_contiguous()
-            and p.is_contiguous() and q.shape[1] == p.shape[1] and q.data_ptr() % 16 == 0 and p.data_ptr() % 16 == 0):
-        return False
-    return bool(_lib.load().rpo_sim_topk_filter_ok(q.shape[0], p.shape[0], q.shape[1]))
+    return _frame_takes(q, p, (torch.bfloat16, torch.float16), 1, _lib.load().rpo_sim_topk_filter_ok)
 
 
 class SearchWorkspace:
@@ -1992,14 +2003,38 @@ def similarity_f32(q, p):
     """f32 scores [Q, P] of bf16 (or fp16) operands, UNROUNDED f32 sums in the 256 x 256 scoring frame's summation order (rpo_sim_scores_f32):
     the score matrix of an f32 index whose embeddings are exact in bf16 (retrieval.FlatIPIndex).  Shapes: search_filter_takes."""
     _need_gpu(q, p)
-    lib = _lib.load()
     if not search_filter_takes(q, p):
         raise ValueError("similarity_f32: bf16 [rows, d] operands of a shape the 256 x 256 scoring kernel takes (search_filter_takes)")
+    return _scores_f32("rpo_sim_scores_f32", q, p, q.shape[1], _dt(q))
+
+
+def _scores_f32(entry: str, q, p, d: int, *dtype):
+    """f32 [Q, P] out of the frame's score-matrix entry `entry` (rpo_sim_scores_f32 takes the operands' dtype behind d, the plane
+    entry none); the caller has asked the operand predicate."""
     scores = torch.empty((q.shape[0], p.shape[0]), dtype=torch.float32, device=q.device)
     with torch.cuda.device(q.device):
-        check(lib.rpo_sim_scores_f32(q.data_ptr(), p.data_ptr(), q.shape[0], p.shape[0], q.shape[1], _dt(q), scores.data_ptr(),
-                                     scores.stride(0), _stream(q)), "rpo_sim_scores_f32")
+        check(getattr(_lib.load(), entry)(q.data_ptr(), p.data_ptr(), q.shape[0], p.shape[0], d, *dtype, scores.data_ptr(),
+                                          scores.stride(0), _stream(q)), entry)
     return scores
+
+
+def _search_step(who: str, entry: str, q, p, d: int, dtype, col0: int, round_scores, best_val, best_idx, ws):
+    """The fused step behind `search_step` / `search_step_planes`: the workspace check, the filter entry `entry` on [rows, d] x
+    [P, d] (`dtype` / `round_scores`: the arguments rpo_sim_topk_filter has behind d and behind k, empty for the plane entry), and
+    rpo_topk_merge_candidates.  The caller has asked the operand predicate."""
+    lib = _lib.load()
+    rows, k = q.shape[0], best_val.shape[1]
+    if (ws.rows, ws.k) != (rows, k) or not _winners_ok(best_val, best_idx, rows, k):
+        raise ValueError(f"{who}: best_val / best_idx must be contiguous f32 / int64 [rows, k] matching the workspace")
+    with torch.cuda.device(q.device):
+        st = _stream(q)
+        check(getattr(lib, entry)(q.data_ptr(), p.data_ptr(), rows, p.shape[0], d, *dtype, int(col0), k, *round_scores,
+                                  best_val.data_ptr(), best_idx.data_ptr(), ws.cand_val.data_ptr(), ws.cand_idx.data_ptr(),
+                                  ws.cand_cnt.data_ptr(), ws.cap, st), entry)
+        check(lib.rpo_topk_merge_candidates(ws.cand_val.data_ptr(), ws.cand_idx.data_ptr(), ws.cand_cnt.data_ptr(), rows, ws.cap, k,
+                                            best_val.data_ptr(), best_idx.data_ptr(), ws.overflow.data_ptr(), st),
+              "rpo_topk_merge_candidates")
+    return best_val, best_idx
 
 
 def search_step(q, p, col0: int, best_val, best_idx, ws: SearchWorkspace, round_scores: bool = True):
@@ -2009,24 +2044,11 @@ def search_step(q, p, col0: int, best_val, best_idx, ws: SearchWorkspace, round_
     then incomplete: the caller redoes the search through `similarity` + `topk_merge`).  round_scores: the score is the sum rounded
     to bf16 once (what `similarity` stores for a bf16 index); False: the f32 sum itself (an f32 index exact in bf16: `similarity_f32`)."""
     _need_gpu(q, p)
-    lib = _lib.load()
     if not search_filter_takes(q, p) or (q.dtype == torch.float16 and round_scores):
         raise ValueError("search_step: bf16 [rows, d] operands (fp16 with round_scores=False) of a shape the 256 x 256 scoring kernel takes "
                          "(search_filter_takes)")
-    rows, d = q.shape
-    k = best_val.shape[1]
-    if (ws.rows, ws.k) != (rows, k) or best_val.shape != (rows, k) or best_idx.shape != (rows, k) or not best_val.is_contiguous() \
-            or not best_idx.is_contiguous() or best_val.dtype != torch.float32 or best_idx.dtype != torch.int64:
-        raise ValueError("search_step: best_val / best_idx must be contiguous f32 / int64 [rows, k] matching the workspace")
-    with torch.cuda.device(q.device):
-        st = _stream(q)
-        check(lib.rpo_sim_topk_filter(q.data_ptr(), p.data_ptr(), rows, p.shape[0], d, _dt(q), int(col0), k, int(bool(round_scores)), best_val.data_ptr(),
-                                      best_idx.data_ptr(), ws.cand_val.data_ptr(), ws.cand_idx.data_ptr(), ws.cand_cnt.data_ptr(),
-                                      ws.cap, st), "rpo_sim_topk_filter")
-        check(lib.rpo_topk_merge_candidates(ws.cand_val.data_ptr(), ws.cand_idx.data_ptr(), ws.cand_cnt.data_ptr(), rows, ws.cap, k,
-                                            best_val.data_ptr(), best_idx.data_ptr(), ws.overflow.data_ptr(), st),
-              "rpo_topk_merge_candidates")
-    return best_val, best_idx
+    return _search_step("search_step", "rpo_sim_topk_filter", q, p, q.shape[1], (_dt(q),), col0, (int(bool(round_scores)),),
+                        best_val, best_idx, ws)
 
 
 # ---- the same search on three bf16 planes of f32 operands (an f32 index that is exact in neither 16-bit type) ----
@@ -2066,48 +2088,25 @@ def split_bf16x3(x):
 def search_planes_takes(qp, cp) -> bool:
     """Shapes the plane-walking frame takes: bf16 [rows, 3 d] planes (split_bf16x3), contiguous and 16-byte aligned, of a problem
     rpo_sim_planes_ok admits: search_filter_takes' shapes applied to d, each operand's planes below 4 GB."""
-    if not (qp.dtype == torch.bfloat16 and cp.dtype == torch.bfloat16 and qp.dim() == 2 and cp.dim() == 2 and qp.is_contiguous()
-            and cp.is_contiguous() and qp.shape[1] == cp.shape[1] and qp.shape[1] % 3 == 0 and qp.data_ptr() % 16 == 0
-            and cp.data_ptr() % 16 == 0):
-        return False
-    return bool(_lib.load().rpo_sim_planes_ok(qp.shape[0], cp.shape[0], qp.shape[1] // 3))
+    return _frame_takes(qp, cp, (torch.bfloat16,), 3, _lib.load().rpo_sim_planes_ok)
 
 
 def similarity_f32_planes(qp, cp):
     """f32 scores [Q, P] of f32 operands given as bf16 planes: exact products of the six leading plane pairs, f32 sums in the
     256 x 256 frame's order, smallest terms first (rpo_sim_scores_f32_planes).  Shapes: search_planes_takes."""
     _need_gpu(qp, cp)
-    lib = _lib.load()
     if not search_planes_takes(qp, cp):
         raise ValueError("similarity_f32_planes: bf16 [rows, 3 d] planes of a shape the plane-walking frame takes (search_planes_takes)")
-    scores = torch.empty((qp.shape[0], cp.shape[0]), dtype=torch.float32, device=qp.device)
-    with torch.cuda.device(qp.device):
-        check(lib.rpo_sim_scores_f32_planes(qp.data_ptr(), cp.data_ptr(), qp.shape[0], cp.shape[0], qp.shape[1] // 3, scores.data_ptr(),
-                                            scores.stride(0), _stream(qp)), "rpo_sim_scores_f32_planes")
-    return scores
+    return _scores_f32("rpo_sim_scores_f32_planes", qp, cp, qp.shape[1] // 3)
 
 
 def search_step_planes(qp, cp, col0: int, best_val, best_idx, ws: SearchWorkspace):
     """`search_step(round_scores=False)` on planes: rpo_sim_topk_filter_planes + rpo_topk_merge_candidates; the scores are those of
     `similarity_f32_planes`, bit for bit."""
     _need_gpu(qp, cp)
-    lib = _lib.load()
     if not search_planes_takes(qp, cp):
         raise ValueError("search_step_planes: bf16 [rows, 3 d] planes of a shape the plane-walking frame takes (search_planes_takes)")
-    rows, d = qp.shape[0], qp.shape[1] // 3
-    k = best_val.shape[1]
-    if (ws.rows, ws.k) != (rows, k) or best_val.shape != (rows, k) or best_idx.shape != (rows, k) or not best_val.is_contiguous() \
-            or not best_idx.is_contiguous() or best_val.dtype != torch.float32 or best_idx.dtype != torch.int64:
-        raise ValueError("search_step_planes: best_val / best_idx must be contiguous f32 / int64 [rows, k] matching the workspace")
-    with torch.cuda.device(qp.device):
-        st = _stream(qp)
-        check(lib.rpo_sim_topk_filter_planes(qp.data_ptr(), cp.data_ptr(), rows, cp.shape[0], d, int(col0), k, best_val.data_ptr(),
-                                             best_idx.data_ptr(), ws.cand_val.data_ptr(), ws.cand_idx.data_ptr(), ws.cand_cnt.data_ptr(),
-                                             ws.cap, st), "rpo_sim_topk_filter_planes")
-        check(lib.rpo_topk_merge_candidates(ws.cand_val.data_ptr(), ws.cand_idx.data_ptr(), ws.cand_cnt.data_ptr(), rows, ws.cap, k,
-                                            best_val.data_ptr(), best_idx.data_ptr(), ws.overflow.data_ptr(), st),
-              "rpo_topk_merge_candidates")
-    return best_val, best_idx
+    return _search_step("search_step_planes", "rpo_sim_topk_filter_planes", qp, cp, qp.shape[1] // 3, (), col0, (), best_val, best_idx, ws)
 
 
 __all__ = ["sim_gemm_nt", "pool_normalize", "topk_merge", "topk_finish", "search_step", "similarity_f32", "search_filter_takes", "search_filter_ok", "SearchWorkspace",

@@ -11,7 +11,7 @@ never materialised, so the corpus size is bounded by the embeddings alone (288 G
 """
 from __future__ import annotations
 
-from typing import List, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -53,6 +53,17 @@ def exact_in_planes(x):
         return None
     planes, inexact = ops.split_bf16x3(x)
     return None if int(inexact.item()) else planes
+
+
+class _Frame(NamedTuple):
+    """How one search scores: the operands and the names of the ops (looked up on `ops` at call time) of one kernel frame."""
+    q: torch.Tensor             # the queries as the frame takes them
+    corpus: Optional[torch.Tensor]      # the corpus likewise, chunked by rows; None: the plain kernel on `emb` only
+    takes: Optional[str]        # operand predicate asked per chunk; None: decided for all chunks up front
+    scores: str                 # the frame's score matrix of a chunk
+    step: Optional[str]         # the fused filter step
+    step_args: dict
+    planes: bool                # the plane frame: one schedule (the fused one) for every walk
 
 
 class FlatIPIndex:
@@ -142,65 +153,53 @@ class FlatIPIndex:
         # 1024 queries), no second pass over it.  A candidate list that runs over (a corpus whose later rows keep beating everything
         # before them) raises the workspace's flag and the search is redone the plain way.
         fused = self.fused and split == 1
-        if getattr(self, "emb_planes", None) is not None:
-            out = self._search_planes(q, k, split, fused)
-            if out is not None:
-                return out
-        # f32 index exact in bf16 + queries exact in bf16: the bf16 kernel frame with f32 scores (class docstring)
-        q16 = exact_in_16(q, self.emb16.dtype) if self.emb16 is not None and q.shape[0] > 0 else None
-        frame = q16 is not None or self.emb.dtype == torch.bfloat16
-        top = idx = ws = None
-        for c0, c1 in self.chunk_schedule(q.shape[0], k, fused and frame):
-            qq, chunk = (q16, self.emb16[c0:c1]) if q16 is not None else (q, self.emb[c0:c1])
-            takes = frame and ops.search_filter_takes(qq, chunk)
-            if fused and c0 >= k and takes:
-                ws = ws or ops.SearchWorkspace(q.shape[0], k, q.device)
-                ops.search_step(qq, chunk, c0, top, idx, ws, round_scores=q16 is None)
-                continue
-            if q16 is not None:                                                 # [nq, chunk] f32: the same frame where it applies, else the f32 kernel
-                scores = ops.similarity_f32(qq, chunk) if takes else ops.similarity(q, self.emb[c0:c1])
+        fr = self._planes_frame(q, k) if getattr(self, "emb_planes", None) is not None else None
+        if fr is None:
+            # f32 index exact in bf16 / fp16 + queries exact in that type: the 16-bit kernel frame with f32 scores (class docstring)
+            q16 = exact_in_16(q, self.emb16.dtype) if self.emb16 is not None and q.shape[0] > 0 else None
+            if q16 is not None:
+                fr = _Frame(q16, self.emb16, "search_filter_takes", "similarity_f32", "search_step", {"round_scores": False}, False)
+            elif self.emb.dtype == torch.bfloat16:
+                fr = _Frame(q, self.emb, "search_filter_takes", "similarity", "search_step", {"round_scores": True}, False)
             else:
-                scores = ops.similarity(q, chunk)                               # [nq, chunk]  (HIP MFMA kernel)
-            top, idx = ops.topk_merge(scores, c0, top, idx, k, split=split)     # HIP selection kernel
-        if ws is not None and int(ws.overflow.item()):
+                fr = _Frame(q, None, None, "similarity", None, {}, False)
+        # the plane frame keeps the fused schedule whatever the walk; the others take it for a fused walk only
+        sched = self.chunk_schedule(q.shape[0], k, fr.planes or (fused and fr.corpus is not None))
+        top, idx, ws = self._walk(q, k, split, fr, sched, fused)
+        if ws is not None and int(ws.overflow.item()):              # redo through the score matrix: planes on the same chunks, else plain
             self.fused_overflows += 1
-            saved, self.fused = self.fused, False
-            try:
-                return self.search(q, k)
-            finally:
-                self.fused = saved
+            top, idx, _ = self._walk(q, k, split, fr, sched if fr.planes else self.chunk_schedule(q.shape[0], k, False), False)
         return ops.topk_finish(top, idx, split)
 
-    def _search_planes(self, q, k, split, fused):
-        """search() on `emb_planes`: the queries are split per call; None (the caller goes on to the f32 kernel) when they are not exact
-        in three planes or a chunk is not of a shape the plane frame takes.  The chunks are those of the fused schedule either way; the
-        first goes through the frame's score matrix + topk_merge, the later ones through the fused step (fused) or the score matrix too,
-        so every score of a search comes out of one summation order.  A candidate overflow redoes the walk through the score matrix."""
+    def _walk(self, q, k, split, fr, sched, fused):
+        """One pass over the chunks of `sched` with the frame `fr`: (winners, indices, the fused steps' workspace or None).  A chunk the
+        frame takes goes through the fused step once the winners hold k entries (fused), else through the frame's score matrix +
+        topk_merge; a chunk it does not take through `similarity` on the index's own rows."""
+        top = idx = ws = None
+        for c0, c1 in sched:
+            chunk = fr.corpus[c0:c1] if fr.corpus is not None else None
+            takes = chunk is not None and (fr.takes is None or getattr(ops, fr.takes)(fr.q, chunk))
+            if fused and c0 >= k and takes:
+                ws = ws or ops.SearchWorkspace(q.shape[0], k, q.device)
+                getattr(ops, fr.step)(fr.q, chunk, c0, top, idx, ws, **fr.step_args)
+                continue
+            scores = getattr(ops, fr.scores)(fr.q, chunk) if takes else ops.similarity(q, self.emb[c0:c1])   # [nq, chunk]  (HIP MFMA kernel)
+            top, idx = ops.topk_merge(scores, c0, top, idx, k, split=split)     # HIP selection kernel
+        return top, idx, ws
+
+    def _planes_frame(self, q, k):
+        """The frame of a search on `emb_planes`: the queries are split per call; None (search goes on to the other frames) when they
+        are not exact in three planes or a chunk of the fused schedule is not of a shape the plane frame takes.  The first chunk goes
+        through the frame's score matrix + topk_merge, the later ones through the fused step (fused) or the score matrix too, so
+        every score of a search comes out of one summation order."""
         if q.shape[0] == 0 or q.shape[1] != self.emb.shape[1]:
             return None
         qp, inexact = ops.split_bf16x3(q)
         if int(inexact.item()):
             return None
-        sched = self.chunk_schedule(q.shape[0], k, True)
-        if not all(ops.search_planes_takes(qp, self.emb_planes[c0:c1]) for c0, c1 in sched):
+        if not all(ops.search_planes_takes(qp, self.emb_planes[c0:c1]) for c0, c1 in self.chunk_schedule(q.shape[0], k, True)):
             return None
-
-        def walk(fused):
-            top = idx = ws = None
-            for c0, c1 in sched:
-                if fused and c0 >= k:
-                    ws = ws or ops.SearchWorkspace(q.shape[0], k, q.device)
-                    ops.search_step_planes(qp, self.emb_planes[c0:c1], c0, top, idx, ws)
-                    continue
-                scores = ops.similarity_f32_planes(qp, self.emb_planes[c0:c1])
-                top, idx = ops.topk_merge(scores, c0, top, idx, k, split=split)
-            return top, idx, ws
-
-        top, idx, ws = walk(fused)
-        if ws is not None and int(ws.overflow.item()):
-            self.fused_overflows += 1
-            top, idx, _ = walk(False)
-        return ops.topk_finish(top, idx, split)
+        return _Frame(qp, self.emb_planes, None, "similarity_f32_planes", "search_step_planes", {}, True)
 
 
 def create_faiss_index(embeddings, device="cuda:0", f32_planes: bool = False):

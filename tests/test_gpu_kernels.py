@@ -900,6 +900,167 @@ def test_fused_search_step_argument_checks():
     torch.cuda.synchronize()
 
 
+def test_sim_frame_entries_refuse_what_they_refused():
+    """One row per refusal of the seven C entries of the 256 x 256 frame, each with its status as a literal (-1 RPO_ERR_INVALID_ARG,
+    -2 RPO_ERR_UNSUPPORTED; 0 / 1 for the two shape predicates), and rows where two faults coincide: which of the two an entry
+    answers is part of its contract.  Every call refuses, so no kernel runs and nothing is dereferenced: the operands are one small
+    buffer whatever the sizes say."""
+    from rankpo_amd import _lib
+    lib = _lib.load()
+    st = torch.cuda.current_stream().cuda_stream
+    buf = torch.zeros(4096, device=DEV, dtype=torch.bfloat16)
+    x, odd = buf.data_ptr(), buf.data_ptr() + 8                     # 16-byte aligned / not
+    assert x % 16 == 0
+    BF, F16, F32 = 1, 2, 0
+    Q, P, D = 256, 49_152, 128                                      # 192 tiles: the least the frame takes
+    BIGR = 256 * 46_341                                             # 46 341^2 tiles > 0x7fffffff; BIGR x 64 bf16 stays below 4 GB
+    G4 = 1 << 25                                                    # G4 rows x 64 bf16 = 4 GB: the 32-bit piece offsets end here
+    PL4 = 1 << 23                                                   # PL4 x 128: 2 GB per plane (the bf16 frame takes it), 6 GB of planes
+
+    # ---- the two shape predicates
+    ok, pok = lib.rpo_sim_topk_filter_ok, lib.rpo_sim_planes_ok
+    for fn in (ok, pok):
+        assert fn(Q, P, D) == 1
+        assert fn(257, 24_576, 64) == 1                             # 2 x 96 tiles
+        assert fn(0, P, D) == 0
+        assert fn(Q, 0, D) == 0
+        assert fn(Q, P, 0) == 0
+        assert fn(-1, P, D) == 0
+        assert fn(Q, P, 100) == 0                                   # d % 64
+        assert fn(Q, P, 96) == 0
+        assert fn(64, P, D) == 0                                    # <= 64 query rows: the skinny kernel
+        assert fn(Q, P - 256, D) == 0                               # 191 tiles
+        assert fn(Q, 1 << 24, D) == 0                               # corpus operand of 4 GB
+        assert fn(1 << 24, P, D) == 0                               # query operand of 4 GB
+    assert ok(BIGR, BIGR, 64) == 1 and pok(BIGR, BIGR, 64) == 0     # the shape rule admits it; the entries refuse the tile count
+    assert ok(Q, PL4, D) == 1 and pok(Q, PL4, D) == 0               # the planes' own bound: rows * 3 d * 2 bytes below 4 GB
+    assert ok(PL4, Q, D) == 1 and pok(PL4, Q, D) == 0
+    assert pok(Q, (1 << 32) // (6 * D) - 1, D) == 1 and pok(Q, (1 << 32) // (6 * D) + 1, D) == 0
+
+    # ---- rpo_sim_gemm_nt(a, rows_a, lda, b, rows_b, ldb, K, c, ldc)
+    def gemm(a=x, rows_a=256, lda=64, b=x, rows_b=256, ldb=64, K=64, c=x, ldc=256):
+        return lib.rpo_sim_gemm_nt(a, rows_a, lda, b, rows_b, ldb, K, c, ldc, st)
+    assert gemm(a=None) == -1
+    assert gemm(b=None) == -1
+    assert gemm(c=None) == -1
+    assert gemm(rows_a=0) == -1
+    assert gemm(rows_b=0) == -1
+    assert gemm(K=0) == -1
+    assert gemm(rows_a=-256) == -1
+    assert gemm(K=96, lda=96, ldb=96) == -2                         # K % 64
+    assert gemm(lda=68) == -2                                       # lda % 8
+    assert gemm(ldb=68) == -2
+    assert gemm(ldc=260) == -2
+    assert gemm(K=128, lda=64, ldb=128) == -2                       # lda < K
+    assert gemm(K=128, lda=128, ldb=64) == -2                       # ldb < K
+    assert gemm(ldc=248) == -2                                      # ldc < rows_a
+    assert gemm(a=odd) == -2
+    assert gemm(b=odd) == -2
+    assert gemm(c=odd) == -2
+    assert gemm(rows_a=BIGR, rows_b=BIGR, ldc=BIGR) == -2           # more than 0x7fffffff tiles
+    assert gemm(rows_a=G4, ldc=G4) == -2                            # a of 4 GB
+    assert gemm(rows_b=G4) == -2                                    # b of 4 GB
+    assert gemm(a=None, K=96) == -1                                 # null pointer + bad shape
+    assert gemm(c=None, ldc=248, a=odd) == -1                       # null pointer + bad stride + misalignment
+    assert gemm(K=0, lda=68) == -1
+
+    # ---- rpo_sim_topk_filter(q, p, Q, P, d, dtype, col0, k, round_scores, best_val, best_idx, cand_val, cand_idx, cand_cnt, cap)
+    def filt(q=x, p=x, Q=Q, P=P, d=D, dt=BF, col0=0, k=4, rnd=1, bv=x, bi=x, cv=x, ci=x, cc=x, cap=1024):
+        return lib.rpo_sim_topk_filter(q, p, Q, P, d, dt, col0, k, rnd, bv, bi, cv, ci, cc, cap, st)
+    for name in ("q", "p", "bv", "bi", "cv", "ci", "cc"):
+        assert filt(**{name: None}) == -1, name
+    for name in ("Q", "P", "d", "k", "cap"):
+        assert filt(**{name: 0}) == -1, name
+        assert filt(**{name: -1}) == -1, name
+    assert filt(col0=-1) == -1
+    assert filt(dt=F32) == -1                                       # f32 operands: not this kernel's
+    assert filt(dt=7) == -1
+    assert filt(dt=F16, rnd=1) == -2                                # fp16 operands: f32 scores only
+    assert filt(q=odd) == -2
+    assert filt(p=odd) == -2
+    assert filt(q=odd, rnd=0) == -2
+    assert filt(p=odd, dt=F16, rnd=0) == -2
+    assert filt(d=96) == -2
+    assert filt(Q=64) == -2
+    assert filt(P=P - 256) == -2
+    assert filt(P=1 << 24) == -2                                    # corpus chunk of 4 GB
+    assert filt(Q=BIGR, P=BIGR, d=64) == -2                         # more than 0x7fffffff tiles
+    assert filt(Q=BIGR, P=BIGR, d=64, dt=F16, rnd=0) == -2
+    assert filt(q=None, d=96) == -1                                 # null pointer + bad shape
+    assert filt(cc=None, Q=64, p=odd) == -1
+    assert filt(dt=F32, q=odd) == -1                                # bad dtype + misalignment
+    assert filt(dt=F32, d=96) == -1                                 # bad dtype + bad shape
+    assert filt(dt=F16, rnd=1, q=odd) == -2                         # fp16 + round_scores + misalignment
+    assert filt(dt=F16, rnd=1, q=None) == -1                        # ... + null pointer
+    assert filt(dt=F16, rnd=1, k=0) == -1
+    assert filt(col0=-1, P=P - 256) == -1
+
+    # ---- rpo_sim_scores_f32(q, p, Q, P, d, dtype, scores, ldc)
+    def sc(q=x, p=x, Q=Q, P=P, d=D, dt=BF, out=x, ldc=P):
+        return lib.rpo_sim_scores_f32(q, p, Q, P, d, dt, out, ldc, st)
+    for name in ("q", "p", "out"):
+        assert sc(**{name: None}) == -1, name
+    for name in ("Q", "P", "d"):
+        assert sc(**{name: 0}) == -1, name
+    assert sc(ldc=P - 1) == -1                                      # ldc < P
+    assert sc(dt=F32) == -1
+    assert sc(dt=7) == -1
+    assert sc(q=odd) == -2
+    assert sc(p=odd, dt=F16) == -2
+    assert sc(d=96) == -2
+    assert sc(Q=64) == -2
+    assert sc(P=P - 256, ldc=P) == -2
+    assert sc(Q=BIGR, P=BIGR, d=64, ldc=BIGR) == -2                 # more than 0x7fffffff tiles
+    assert sc(Q=BIGR, P=BIGR, d=64, ldc=BIGR, dt=F16) == -2
+    assert sc(q=None, d=96) == -1                                   # null pointer + bad shape
+    assert sc(dt=F32, p=odd) == -1                                  # bad dtype + misalignment
+    assert sc(ldc=P - 1, Q=64) == -1                                # ldc < P + a refused shape
+    assert sc(ldc=P - 1, q=odd) == -1
+
+    # ---- rpo_sim_topk_filter_planes(q, p, Q, P, d, col0, k, best_val, best_idx, cand_val, cand_idx, cand_cnt, cap)
+    def pfilt(q=x, p=x, Q=Q, P=P, d=D, col0=0, k=4, bv=x, bi=x, cv=x, ci=x, cc=x, cap=1024):
+        return lib.rpo_sim_topk_filter_planes(q, p, Q, P, d, col0, k, bv, bi, cv, ci, cc, cap, st)
+    for name in ("q", "p", "bv", "bi", "cv", "ci", "cc"):
+        assert pfilt(**{name: None}) == -1, name
+    for name in ("Q", "P", "d", "k", "cap"):
+        assert pfilt(**{name: 0}) == -1, name
+        assert pfilt(**{name: -1}) == -1, name
+    assert pfilt(col0=-1) == -1
+    assert pfilt(q=odd) == -2
+    assert pfilt(p=odd) == -2
+    assert pfilt(d=96) == -2
+    assert pfilt(Q=64) == -2
+    assert pfilt(P=P - 256) == -2
+    assert pfilt(P=PL4) == -2                                       # the planes' own bound: corpus planes of 6 GB
+    assert pfilt(Q=PL4, P=256) == -2                                # query planes of 6 GB
+    assert pfilt(Q=BIGR, P=BIGR, d=64) == -2
+    assert pfilt(q=None, d=96) == -1                                # null pointer + bad shape
+    assert pfilt(bi=None, P=PL4) == -1
+    assert pfilt(col0=-1, p=odd) == -1
+    assert pfilt(k=0, Q=64) == -1
+
+    # ---- rpo_sim_scores_f32_planes(q, p, Q, P, d, scores, ldc)
+    def psc(q=x, p=x, Q=Q, P=P, d=D, out=x, ldc=P):
+        return lib.rpo_sim_scores_f32_planes(q, p, Q, P, d, out, ldc, st)
+    for name in ("q", "p", "out"):
+        assert psc(**{name: None}) == -1, name
+    for name in ("Q", "P", "d"):
+        assert psc(**{name: 0}) == -1, name
+    assert psc(ldc=P - 1) == -1
+    assert psc(q=odd) == -2
+    assert psc(p=odd) == -2
+    assert psc(d=96) == -2
+    assert psc(Q=64) == -2
+    assert psc(P=P - 256, ldc=P) == -2
+    assert psc(P=PL4, ldc=PL4) == -2                                # the planes' own bound
+    assert psc(Q=PL4, P=256, ldc=256) == -2
+    assert psc(q=None, d=96) == -1                                  # null pointer + bad shape
+    assert psc(ldc=P - 1, Q=64) == -1                               # ldc < P + a refused shape
+    assert psc(ldc=PL4 - 1, P=PL4) == -1                            # ldc < P + the planes' bound
+    assert psc(ldc=P - 1, p=odd) == -1
+    torch.cuda.synchronize()
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("N,L,d", [(600, 512, 2048), (1024, 33, 384), (513, 1000, 4096), (2000, 7, 64), (700, 128, 1024)])
 def test_pool_normalize_one_wave_per_sample_kernel(dtype, N, L, d):
